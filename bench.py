@@ -2,7 +2,14 @@
 """Benchmark: individual·loci per second per EM iteration of the HaploModel EM
 (BASELINE.json metric) on synthetic founder-mosaic panels.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run does what the headline needs and no more: panel, M0, W warmup
+steps, K timed steps, the result line.  `--full` adds the legs with runs of
+their own — the sampled CPU baseline (and `--cpu-validate`), the steady leg
+(`value_steady`) — and the roofline blocks with the committed counter
+summaries under profiles/; without it those fields of the line are null.
+`--dump-outputs DIR` writes what the last timed step returned (dump_outputs).
 
 Workload: BASELINE.json configs[2] — 10 000 individuals x 2 000 biallelic SNP
 loci (cfg 3, seed 3; the largest configuration quoted for one MI355X), reference
@@ -60,7 +67,7 @@ DBL_MAX = sys.float_info.max
 # few % of peak; its VALU issue (SQ_INSTS_VALU, tools/sq_summary.py) is the
 # roof it runs against.
 # The sampled CPU estimate checked against the whole single-thread chain at
-# cfg 2 (bench.py --config 2 --cpu-validate on a GPU box, same run).
+# cfg 2 (bench.py --full --config 2 --cpu-validate on a GPU host, same run).
 VALIDATION_NOTE = "profiles/r04/cpu_validate_cfg2.json"
 LIMITER = ("VALU issue of the segmented k-best selection: the SIMDs' VALU issue slots measured busy "
            "(4 x (SQ_INSTS_VALU - SQ_ACTIVE_INST_VALU2) over 32 SIMDs x SQ_BUSY_CYCLES per SE; dual issue calibrated "
@@ -81,9 +88,15 @@ def parse():
     ap.add_argument("--missing", type=float, default=0.0, help="missing-allele rate of the synthetic panel")
     ap.add_argument("--seed", type=int, default=0, help="panel seed (default = config index)")
     ap.add_argument("--sample-size", type=int, default=10)
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs beside the headline: the sampled CPU baseline, the steady leg and the "
+                         "roofline blocks (a plain run reports them as null)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned as DIR/<name>.npy "
+                         "(float32 / float64, at most 64 MB; large arrays as a fixed seeded sample of rows)")
     ap.add_argument("--steady-steps", type=int, default=None,
-                    help="forced iterations after the chain's end, timed for value_steady (0: skip)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+                    help="with --full: forced iterations after the chain's end, timed for value_steady (0: skip)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--cpu-indiv", type=int, default=20, help="individuals per CPU E-step sample (E_k, k >= 2)")
     ap.add_argument("--cpu-indiv-e1", type=int, default=24,
                     help="individuals of the CPU E_1 sample (M0 model); timed in two interleaved halves for the spread")
@@ -98,11 +111,18 @@ def parse():
                     help="M-step collective: RCCL (the product), or a gloo host all-reduce with every rank on "
                          "GPU LOCAL_RANK %% device_count (rehearses the multi-rank bench on one GPU; not a measurement)")
     a = ap.parse_args()
+    if not a.full and (a.cpu_validate or (a.steady_steps or 0) > 0):
+        ap.error("--cpu-validate and --steady-steps N > 0 are legs of a --full run")
     big = a.config == 4  # an E1 of ~25 s per rank at 8 ranks: one chain, no steady leg, no CPU sample
     a.steps = a.steps if a.steps is not None else (3 if big else 20)
     a.warmup = a.warmup if a.warmup is not None else (1 if big else 5)
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     a.steady_steps = a.steady_steps if a.steady_steps is not None else (0 if big else 8)
     if big:
+        a.no_cpu_baseline = True
+    if not a.full:  # a plain run: the headline only
+        a.steady_steps = 0
         a.no_cpu_baseline = True
     c = synth.CONFIGS[a.config]
     a.N = a.individuals or c["N"]
@@ -234,6 +254,7 @@ def main():
 
     chain = {"it": 0, "old_ll": -DBL_MAX, "ended": False}
     run_log = []  # (R_E, value-pass launches) of every E-step this process runs after M0, in order (PMC pairing)
+    iter_logs = []  # what em_iteration returned, every step in order (--dump-outputs)
 
     def em_step(force_m: bool = False):
         """One step of the converged chain (or, force_m, an iteration that
@@ -253,6 +274,7 @@ def main():
         ms_stats = m.mine_stats() if go or force_m else {"reduction_ms": 0.0, "reduction_levels": 0}
         win = m.estep_windows()
         run_log.append([int(log["r_e"]), int(sp["value_passes"])])
+        iter_logs.append((it, bool(go), log))
         progress(f"EM iteration {it}: LL {log['log_likelihood']:.6f}, R_E {log['r_e']}, "
                  f"E {t['estep_forward_ms'] + t['estep_traceback_ms']:.0f} ms "
                  f"(structure {sp['structure_ms']:.0f} in {sp['structure_passes']}, values {sp['values_ms']:.0f} in "
@@ -280,6 +302,8 @@ def main():
     elapsed = max_over_ranks(time.perf_counter() - t0)
     ms_per_step = elapsed / args.steps * 1e3
     value = N * L / (elapsed / args.steps)
+    if args.dump_outputs and rank == 0:  # before any later leg runs another E-step
+        dump_outputs(args.dump_outputs, m, iter_logs[-args.steps:])
 
     # whole chains inside the timed region (per-step walls are this rank's;
     # every step ends in a collective, so ranks stay in step)
@@ -310,38 +334,74 @@ def main():
         steady = {"value": N * L / (el / args.steady_steps), "ms_per_step": el / args.steady_steps * 1e3,
                   "iterations": [s["iteration"] for s in st]}
 
-    # Roofline of the dominant kernel, the E-step value pass (estep_values):
-    # SURVEY.md §8d prices the E-step at 8 B per retained k-best link (R_E); the
-    # value pass owns that term.  Per launch: algorithmic bytes / HIP-event
-    # duration on the context stream, summed over the timed launches (a large
-    # E-step runs its individuals in several groups, one launch each).
-    r_e_all = sum_over_ranks(float(sum(s["r_e"] for s in steps)))
-    val_ms = max_over_ranks(sum(s["values_ms"] for s in steps))
-    n_launch = sum(s["value_passes"] for s in steps)
-    achieved = 8.0 * r_e_all / (val_ms * 1e-3) / 1e9 / world if val_ms > 0 else 0.0
-    # Roofline of the whole iteration: B_iter = 2NL (genotypes)
-    # + 2HL (samples written by E, read by M) + 8 R_E + 1 R_M, over t_iter.
-    H_all = sum_over_ranks(float(sum(s["H"] for s in steps)))
-    r_m_all = sum_over_ranks(float(sum(s["r_m"] for s in steps)))  # each rank scans its own samples
-    b_iter = (2.0 * N * L * args.steps + 2.0 * H_all * L + 8.0 * r_e_all + r_m_all) / args.steps
-    ach_iter = b_iter / (elapsed / args.steps) / 1e9
-    pmc = pmc_summary(args.tag, ident)
-    sq = sq_summary(args.tag, ident)
-    # the bound from the evidence: the fraction of the VALU issue roof the SQ
-    # pass measured against the fraction of HBM bandwidth the PMC pass measured
-    hbm_frac_meas = None
-    if pmc and pmc.get("hbm_bytes_per_launch") and val_ms > 0 and n_launch:
-        hbm_frac_meas = pmc["hbm_bytes_per_launch"] / (val_ms * 1e-3 / n_launch) / 1e9 / HBM_PEAK_GBS
-    # (only counters of the library this process loaded count as evidence;
-    # without them the line prices against HBM and says the bound is unmeasured)
-    bound, bound_basis = "hbm", "no same-build counters: priced against HBM, limiter unmeasured"
-    if sq and sq["same_build"] and sq.get("valu_issue_frac") is not None:
-        hbm_f = hbm_frac_meas or achieved / HBM_PEAK_GBS
-        bound = "valu-issue" if sq["valu_issue_frac"] > hbm_f else "hbm"
-        if max(sq["valu_issue_frac"], hbm_f) < 0.5:  # neither roof near: the waves wait (SQ_WAIT_ANY)
-            bound = "latency"
-        bound_basis = (f"measured VALU issue occupancy {sq['valu_issue_frac']:.2f} vs HBM fraction {hbm_f:.2f} "
-                       f"({'PMC' if hbm_frac_meas else 'algorithmic bytes'}), same build")
+    def roofline_blocks():
+        """--full: the roofline of estep_values and of the whole iteration, from
+        the timed steps' own counts and times and the committed counter
+        summaries of the same library build (collective: every rank calls it)."""
+        # Roofline of the dominant kernel, the E-step value pass (estep_values):
+        # SURVEY.md §8d prices the E-step at 8 B per retained k-best link (R_E); the
+        # value pass owns that term.  Per launch: algorithmic bytes / HIP-event
+        # duration on the context stream, summed over the timed launches (a large
+        # E-step runs its individuals in several groups, one launch each).
+        r_e_all = sum_over_ranks(float(sum(s["r_e"] for s in steps)))
+        val_ms = max_over_ranks(sum(s["values_ms"] for s in steps))
+        n_launch = sum(s["value_passes"] for s in steps)
+        achieved = 8.0 * r_e_all / (val_ms * 1e-3) / 1e9 / world if val_ms > 0 else 0.0
+        # Roofline of the whole iteration (SURVEY.md §8d): B_iter = 2NL (genotypes)
+        # + 2HL (samples written by E, read by M) + 8 R_E + 1 R_M, over t_iter.
+        H_all = sum_over_ranks(float(sum(s["H"] for s in steps)))
+        r_m_all = sum_over_ranks(float(sum(s["r_m"] for s in steps)))  # each rank scans its own samples
+        b_iter = (2.0 * N * L * args.steps + 2.0 * H_all * L + 8.0 * r_e_all + r_m_all) / args.steps
+        ach_iter = b_iter / (elapsed / args.steps) / 1e9
+        pmc = pmc_summary(args.tag, ident)
+        sq = sq_summary(args.tag, ident)
+        # the bound from the evidence: the fraction of the VALU issue roof the SQ
+        # pass measured against the fraction of HBM bandwidth the PMC pass measured
+        hbm_frac_meas = None
+        if pmc and pmc.get("hbm_bytes_per_launch") and val_ms > 0 and n_launch:
+            hbm_frac_meas = pmc["hbm_bytes_per_launch"] / (val_ms * 1e-3 / n_launch) / 1e9 / HBM_PEAK_GBS
+        # (only counters of the library this process loaded count as evidence;
+        # without them the line prices against HBM and says the bound is unmeasured)
+        bound, bound_basis = "hbm", "no same-build counters: priced against HBM, limiter unmeasured"
+        if sq and sq["same_build"] and sq.get("valu_issue_frac") is not None:
+            hbm_f = hbm_frac_meas or achieved / HBM_PEAK_GBS
+            bound = "valu-issue" if sq["valu_issue_frac"] > hbm_f else "hbm"
+            if max(sq["valu_issue_frac"], hbm_f) < 0.5:  # neither roof near: the waves wait (SQ_WAIT_ANY)
+                bound = "latency"
+            bound_basis = (f"measured VALU issue occupancy {sq['valu_issue_frac']:.2f} vs HBM fraction {hbm_f:.2f} "
+                           f"({'PMC' if hbm_frac_meas else 'algorithmic bytes'}), same build")
+        roofline = {
+            "bound": bound, "bound_basis": bound_basis, "kernel": "estep_values",
+            "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS,
+            "traffic": pmc.get("hbm_bytes_per_launch") if pmc and pmc["same_build"] else None,
+            "traffic_over_alg": pmc.get("traffic_over_alg") if pmc and pmc["same_build"] else None,
+            "traffic_source": pmc.get("source") if pmc else None,
+            "traffic_same_build": pmc["same_build"] if pmc else None,
+            "hbm_frac_measured": hbm_frac_meas if pmc and pmc["same_build"] else None,
+            "valu_issue_frac": sq["valu_issue_frac"] if sq and sq["same_build"] else None,
+            "valu_dual_issue_share": sq["valu_dual_issue_share"] if sq and sq["same_build"] else None,
+            "valu_issue_frac_nominal_4cyc": sq["valu_issue_frac_nominal_4cyc"] if sq and sq["same_build"] else None,
+            "valu_issue_frac_nominal_2cyc": sq["valu_issue_frac_nominal_2cyc"] if sq and sq["same_build"] else None,
+            "lds_bank_conflict_ratio": sq["lds_bank_conflict_ratio"] if sq and sq["same_build"] else None,
+            "valu_issue_source": sq.get("source") if sq else None,
+            "valu_issue_same_build": sq["same_build"] if sq else None,
+            "valu_issue_formula": "4 * (SQ_INSTS_VALU - SQ_ACTIVE_INST_VALU2) / (32 SIMDs per SE * SQ_BUSY_CYCLES): "
+                                  "measured VALU issue-slot occupancy (one instruction per quad-cycle, two when "
+                                  "they dual-issue; profiles/r06/issue/)",
+            "limiter": LIMITER,
+            "alg_bytes_per_launch": 8.0 * r_e_all / world / max(1, n_launch),
+            "avg_launch_ms": val_ms / max(1, n_launch),
+            "launches": n_launch,
+            "per_unit": "8 B per retained k-best link (R_E)",
+        }
+        roofline_iter = {
+            "bound": "hbm", "achieved": ach_iter, "peak": HBM_PEAK_GBS * world, "unit": "GB/s",
+            "frac": ach_iter / (HBM_PEAK_GBS * world), "bytes_per_iter": b_iter,
+            "formula": "B_iter = 2NL + 2HL + 8 R_E + R_M (SURVEY.md 8d), / t_iter",
+        }
+        return roofline, roofline_iter
+
+    roofline, roofline_iter = roofline_blocks() if args.full else (None, None)
 
     if rank == 0:
         line = {
@@ -372,36 +432,10 @@ def main():
             "value_chain": value_chain,
             "chain": {"iterations": [len(c) for c in chains],
                       "ms_per_iteration": chain_s / chain_iters * 1e3 if chain_iters else None},
+            "full": args.full,  # false: value_steady, roofline, roofline_iter and cpu_baseline were not run (null)
             "value_steady": steady,
-            "roofline": {
-                "bound": bound, "bound_basis": bound_basis, "kernel": "estep_values",
-                "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS,
-                "traffic": pmc.get("hbm_bytes_per_launch") if pmc and pmc["same_build"] else None,
-                "traffic_over_alg": pmc.get("traffic_over_alg") if pmc and pmc["same_build"] else None,
-                "traffic_source": pmc.get("source") if pmc else None,
-                "traffic_same_build": pmc["same_build"] if pmc else None,
-                "hbm_frac_measured": hbm_frac_meas if pmc and pmc["same_build"] else None,
-                "valu_issue_frac": sq["valu_issue_frac"] if sq and sq["same_build"] else None,
-                "valu_dual_issue_share": sq["valu_dual_issue_share"] if sq and sq["same_build"] else None,
-                "valu_issue_frac_nominal_4cyc": sq["valu_issue_frac_nominal_4cyc"] if sq and sq["same_build"] else None,
-                "valu_issue_frac_nominal_2cyc": sq["valu_issue_frac_nominal_2cyc"] if sq and sq["same_build"] else None,
-                "lds_bank_conflict_ratio": sq["lds_bank_conflict_ratio"] if sq and sq["same_build"] else None,
-                "valu_issue_source": sq.get("source") if sq else None,
-                "valu_issue_same_build": sq["same_build"] if sq else None,
-                "valu_issue_formula": "4 * (SQ_INSTS_VALU - SQ_ACTIVE_INST_VALU2) / (32 SIMDs per SE * SQ_BUSY_CYCLES): "
-                                      "measured VALU issue-slot occupancy (one instruction per quad-cycle, two when "
-                                      "they dual-issue; profiles/r06/issue/)",
-                "limiter": LIMITER,
-                "alg_bytes_per_launch": 8.0 * r_e_all / world / max(1, n_launch),
-                "avg_launch_ms": val_ms / max(1, n_launch),
-                "launches": n_launch,
-                "per_unit": "8 B per retained k-best link (R_E)",
-            },
-            "roofline_iter": {
-                "bound": "hbm", "achieved": ach_iter, "peak": HBM_PEAK_GBS * world, "unit": "GB/s",
-                "frac": ach_iter / (HBM_PEAK_GBS * world), "bytes_per_iter": b_iter,
-                "formula": "B_iter = 2NL + 2HL + 8 R_E + R_M (SURVEY.md 8d), / t_iter",
-            },
+            "roofline": roofline,
+            "roofline_iter": roofline_iter,
             "cpu_baseline": cpu,
             "m0": {"seconds": t_m0, "patterns": P0, "r_m": rm0},
             "library": ident,
@@ -412,6 +446,68 @@ def main():
     if world > 1:
         dist.barrier()
         dist.destroy_process_group()
+
+
+DUMP_SEED = 20240607  # row samples of --dump-outputs: the same rows in every run and every build
+DUMP_RESOLUTION_BYTES = 16 << 20  # float32 rows of resolutions
+DUMP_PATTERN_ROWS = 1 << 18
+
+
+def dump_outputs(out_dir, m, logs):
+    """--dump-outputs: what the last timed step left with its caller, as
+    DIR/<name>.npy (float64; resolutions float32), under 64 MB in all.
+
+    iter_log       one row per timed step, what hmc_em_iteration returned
+                   (columns in manifest.json; the last row is the last step)
+    estep_*        the last step's E-step per individual of this rank: total
+                   likelihood, candidates, status, and prior / posterior /
+                   sample weight of each of the `sample_size` candidates
+    resolutions    the accepted haplotype pairs [n, 2, L] (allele symbols) of
+                   a seeded sample of individuals, their indices in
+                   resolutions_rows
+    pattern_*      start, length, frequency, prefix frequency and transition
+                   probability of a seeded sample of the pattern table the step
+                   left (the M-step's when the chain continued), ids in
+                   pattern_rows
+
+    The panel comes from the arguments' seed and the samples from DUMP_SEED,
+    so two builds run with the same arguments write comparable files.  With
+    more than one rank these are rank 0's individuals."""
+    import ctypes as C
+
+    os.makedirs(out_dir, exist_ok=True)
+    cols = ["iteration", "go", "log_likelihood", "n_samples", "n_patterns", "r_e", "r_m", "switch_error", "ihp", "igp"]
+    arrays = {"iter_log": np.array([[it, go] + [log[c] for c in cols[2:]] for it, go, log in logs], np.float64)}
+    for k, v in m.estep_results().items():
+        arrays[f"estep_{k}"] = v.astype(np.float64)
+    rng = np.random.default_rng(DUMP_SEED)
+    res = m.resolutions()
+    n = res.shape[0]
+    rows = np.sort(rng.choice(n, min(n, max(1, DUMP_RESOLUTION_BYTES // (8 * max(1, res.shape[2])))), replace=False))
+    arrays["resolutions"] = res[rows].astype(np.float32)
+    arrays["resolutions_rows"] = rows.astype(np.float64)
+    del res
+    # the table without its allele strings and successor ids (hmc_get_patterns fills what it is given)
+    P, hl = C.c_int(), C.c_int()
+    m._check(hmc_amd.lib().hmc_model_info(m._h, C.byref(P), C.byref(hl)))
+    P = P.value
+    start, length = np.zeros(P, np.int32), np.zeros(P, np.int32)
+    freq, prefix, tp = np.zeros(P), np.zeros(P), np.zeros(P)
+    i32, f64 = C.POINTER(C.c_int32), C.POINTER(C.c_double)
+    m._check(hmc_amd.lib().hmc_get_patterns(m._h, start.ctypes.data_as(i32), length.ctypes.data_as(i32),
+                                            freq.ctypes.data_as(f64), prefix.ctypes.data_as(f64),
+                                            tp.ctypes.data_as(f64), None, None, 0))
+    rows = np.sort(rng.choice(P, min(P, DUMP_PATTERN_ROWS), replace=False))
+    arrays["pattern_rows"] = rows.astype(np.float64)
+    for k, v in (("start", start), ("len", length), ("freq", freq), ("prefix", prefix), ("tp", tp)):
+        arrays[f"pattern_{k}"] = v[rows].astype(np.float64)
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= 64 << 20, total
+    for k, a in arrays.items():
+        np.save(os.path.join(out_dir, k + ".npy"), a)
+    with open(os.path.join(out_dir, "manifest.json"), "w") as f:
+        json.dump({"iter_log_columns": cols, "seed": DUMP_SEED, "patterns": P, "individuals": n, "bytes": total,
+                   "arrays": {k: {"shape": list(a.shape), "dtype": str(a.dtype)} for k, a in arrays.items()}}, f, indent=1)
 
 
 def _profile_json(name, ident):

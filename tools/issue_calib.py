@@ -7,7 +7,7 @@ bench.
 usage: python tools/issue_calib.py DIR [OUT.json]
   DIR holds ib_{BUSY,MIX}/ or ib_{BUSY,MIX}.csv (issue_bench 1024 under --pmc), issue_cpi.json
   (issue_bench stamps), cb_{BUSY,MIX}/ (coop_bench 32 2000 5 10) and
-  b3_{BUSY,MIX}/ (bench.py --config 3 --steps 2 --warmup 0), as written by the
+  b3_{BUSY,MIX}/ (bench.py --full --config 3 --steps 2 --warmup 0), as written by the
   round-6 GPU run (profiles/r06/issue/cmd.sh).
 
 The busy pass counts SQ_INSTS_VALU, SQ_ACTIVE_INST_VALU2 (quad-cycles in which
@@ -77,7 +77,7 @@ def main():
     except (OSError, ValueError):
         pass
     for tag, name in (("cb", "coop_bench mode 5 (seg2_nth_slots, S = 10, 16 waves per CU)"),
-                      ("b3", "bench.py --config 3 --steps 2 --warmup 0")):
+                      ("b3", "bench.py --full --config 3 --steps 2 --warmup 0")):
         try:
             a, sa = load(os.path.join(d, f"{tag}_BUSY"))
             m, _ = load(os.path.join(d, f"{tag}_MIX"))

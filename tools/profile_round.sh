@@ -16,7 +16,7 @@ DEST=$OUT/commit/$TAG
 mkdir -p "$OUT" "$DEST"
 export TMPDIR=/tmp
 K=estep_values
-BENCH="bench.py --config $CFG --no-cpu-baseline"
+BENCH="bench.py --full --config $CFG --no-cpu-baseline"
 echo "[profile] FETCH_SIZE pass" >&2
 timeout -s KILL 500 rocprofv3 --pmc FETCH_SIZE --kernel-include-regex $K --output-format csv \
   -d "$OUT/pmc_fetch" -o f -- python3 $BENCH > "$OUT/pmc_fetch.json" 2> "$OUT/pmc_fetch.err"
@@ -35,7 +35,7 @@ timeout -s KILL 500 rocprofv3 --kernel-trace --stats --output-format csv -d "$OU
   python3 $BENCH > "$OUT/trace.json" 2> "$OUT/trace.err"
 cp "$(find "$OUT/trace" -name "*kernel_stats.csv" | head -n 1)" "$DEST/kernel_stats_cfg$CFG.csv"
 tail -1 "$OUT/trace.json" > "$DEST/bench_under_rocprof_cfg$CFG.json"
-SHORT="bench.py --config $CFG --no-cpu-baseline --steps 2 --warmup 0"
+SHORT="bench.py --full --config $CFG --no-cpu-baseline --steps 2 --warmup 0"
 [ -n "${SKIP_SQ:-}" ] && { echo "[profile] done (SQ passes skipped)" >&2; exit 0; }
 for P in "SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_INSTS_VALU SQ_INSTS_SALU" \
          "SQ_INSTS_LDS SQ_WAIT_INST_LDS SQ_LDS_BANK_CONFLICT SQ_ACTIVE_INST_LDS SQ_ACTIVE_INST_VALU SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_INSTS_SMEM" \
