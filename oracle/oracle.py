@@ -2,7 +2,8 @@
 
 TEST INFRASTRUCTURE ONLY: imported by tests/, __graft_entry__.smoke() and the
 cpu_baseline leg of bench.py, never by the product package hmc_amd.
-Parity unpinned (see hmc_oracle.cpp header and DESIGN.md §Oracle).
+No reference output pins it; tests/enumeration.py checks it against exhaustive
+enumeration at small sizes (see hmc_oracle.cpp header and DESIGN.md §Oracle).
 """
 from __future__ import annotations
 

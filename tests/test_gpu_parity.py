@@ -1305,6 +1305,34 @@ def test_exact_mstep_wide_trie(oracle_mod):
     _assert_table_bits(m.patterns(), po)
 
 
+@pytest.mark.parametrize("width", [9, 10])
+def test_exact_mstep_trie_width_9_and_10(oracle_mod, width):
+    """Trie widths 9 and 10: the allele-pair ballot is on (W (W + 1) / 2 <= 64)
+    while the per-depth LDS cache is off (exact_walk_cache_w returns 0 past 8)
+    — a combination neither `a8` (both on) nor the 20-allele panel (both off)
+    reaches.  Four microsatellite loci with `width` alleles on a 40 x 30 panel;
+    the table equals the restatement's bit for bit."""
+    rng = np.random.default_rng(20 + width)
+    base = synth.founder_mosaic(40, 30, A=2, seed=11)
+    a = np.where(base.alleles < 0, -1, base.alleles - ord("1") + 1).astype(np.int32)
+    for k in (4, 11, 19, 26):
+        a[:, :, k] = rng.integers(1, width + 1, size=(40, 2))
+    p = synth.Panel(alleles=a, types="M" * 30)
+    o = oracle_mod.Oracle(p.alleles, p.types, sample_size=10)
+    o.find_patterns()
+    o.resolve_all()
+    P_o, _ = o.estimate_patterns()
+    po = o.patterns()
+    m = gpu_model(p)
+    m.exact_estimate = True
+    m.find_patterns()
+    m.resolve_all()
+    P_g, _ = m.find_patterns()
+    assert m.amax == width
+    assert P_g == P_o
+    _assert_table_bits(m.patterns(), po)
+
+
 RARE = dict(N=80, L=50, A=2, K=40, rho=0.05, seed=12)  # patterns down to min_freq = 0.2 / 2N = 1.25e-3
 
 
