@@ -1479,10 +1479,17 @@ size_t estep_s2_lds_bytes(int S, int fc, int nw, bool pair) { return (size_t)k2_
 // PAIR: two links per lane in phase B (seg2_nth_slots: S lanes and 64 / S
 // lists of up to 2S links per wavefront, S <= 16) — heavy groups, whose loci
 // have many chains of adds (cfg 3's E1: ~130), get 2x the lists per wave.
-template <bool FAST, int WPE, bool WIDE = false, bool PAIR = false>
+// SC: the sample size fixed at compile time (0: a.S at run time).  Every
+// helper of the pass is inlined (make_seg, seg2_nth_slots, k2_plan, k2_slots,
+// copy_extended_hm, the trace helpers), so segment width, slot bases, clamps,
+// shifts and the per-link loops of phase A fold to constants: the partition
+// loop of the PAIR builds goes from 214-216 to 204-207 instructions at
+// S = 10 (the reference's default; the only fixed size instantiated).
+template <bool FAST, int WPE, bool WIDE = false, bool PAIR = false, int SC = 0>
 __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(WPE))) void estep_values(ValueArgs a) {
   extern __shared__ __align__(16) unsigned char smem[];
-  const int S = a.S, L = a.L, hl = a.head_len;
+  if constexpr (SC > 0) a.S = SC;  // (the trace helpers read a.S)
+  const int S = SC > 0 ? SC : a.S, L = a.L, hl = a.head_len;
   // locus window of trace indices [wlo, whi) (classic: the head to L)
   const int wlo = a.w.hi > 0 ? a.w.lo : hl, whi = a.w.hi > 0 ? a.w.hi : L + 1;
   const bool from_ck = wlo > hl, last_win = whi == L + 1;
@@ -2164,6 +2171,8 @@ hipError_t launch_estep_values(const ValueArgs &a, int grid, int nw, bool fast, 
   const size_t lds = estep_s2_lds_bytes(a.S, a.lds_fc, nw, pair);
   void (*k)(ValueArgs);
   if (a.S > 32) k = estep_values<false, 4, true>;  // lists of more than one wavefront: exact order only
+  else if (pair && a.S == 10)
+    k = wpe == 5 ? estep_values<false, 5, false, true, 10> : estep_values<false, 4, false, true, 10>;
   else if (pair) k = wpe == 5 ? estep_values<false, 5, false, true> : estep_values<false, 4, false, true>;
   else if (wpe == 5) k = fast ? estep_values<true, 5> : estep_values<false, 5>;
   else k = fast ? estep_values<true, 4> : estep_values<false, 4>;

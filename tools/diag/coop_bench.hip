@@ -16,6 +16,8 @@
 //   mode 5: two elements per lane, S lanes per list (seg2_nth_slots)
 //   mode 6: four elements per lane, ceil(S / 2) lanes per list (segE_nth_slots<4>)
 //   mode 7: as mode 5 with lane-major slots (seg2m_nth_slots)
+//   mode 9: as mode 5 with S = 10 fixed at compile time (the product's
+//   estep_values<..., PAIR, 10>: the helpers are inlined, so S folds)
 #include <hip/hip_runtime.h>
 
 #include <cstdio>
@@ -591,9 +593,10 @@ __global__ __launch_bounds__(64) void bench_seg2(int S, int adds, double *out) {
 
 // mode 5: two elements per lane, S lanes per list (seg2_nth_slots); mode 8:
 // the same (the round-4 A/B of the cut from the swap count, now the only one)
-template <bool KCUT>
-__global__ __launch_bounds__(64) void bench_seg2e(int S, int adds, double *out) {
+template <bool KCUT, int SC = 0>
+__global__ __launch_bounds__(64) void bench_seg2e(int S_, int adds, double *out) {
   extern __shared__ unsigned char sm[];
+  const int S = SC > 0 ? SC : S_;
   const int lane = threadIdx.x;
   // slots: (64 / S + 1) x 2S <= 160 per wave (lanes past the last segment
   // address a dead segment of their own)
@@ -654,19 +657,19 @@ int main(int argc, char **argv) {
   // mode 2/3 with wpc / (32 / S) process the same lists.
   const int G = 64 / (2 * S);
   const int lists = mode == 2 || mode == 3 ? cu * wpc * 64 : cu * wpc * G;
-  if (mode < 0 || mode == 1 || mode > 8) return 1;
+  if (mode < 0 || mode == 1 || mode > 9 || (mode == 9 && S != 10)) return 1;
   const int G5 = 64 / S, G6 = 64 / ((2 * S + 3) / 4);
   int grid = mode == 0 ? cu * wpc
                        : (mode == 4 ? cu * wpc / 2
-                                    : (mode == 5 || mode == 7 || mode == 8 ? (lists + G5 - 1) / G5
+                                    : (mode == 5 || mode == 7 || mode == 8 || mode == 9 ? (lists + G5 - 1) / G5
                                                               : (mode == 6 ? (lists + G6 - 1) / G6 : (lists + 63) / 64)));
-  size_t lds = mode == 2 || mode == 3 ? (size_t)2 * S * 64 * 12 : (mode == 4 ? 4096 : (mode == 5 || mode == 7 || mode == 8 ? 4608 : (mode == 6 ? 8448 : 2048)));
+  size_t lds = mode == 2 || mode == 3 ? (size_t)2 * S * 64 * 12 : (mode == 4 ? 4096 : (mode == 5 || mode == 7 || mode == 8 || mode == 9 ? 4608 : (mode == 6 ? 8448 : 2048)));
   void (*kern)(int, int, double *) =
       mode == 0 ? bench_seg
                 : (mode == 2 ? bench_lane<false>
                              : (mode == 3 ? bench_lane<true>
                                           : (mode == 4 ? bench_seg2
-                                                       : (mode == 5 ? bench_seg2e<false> : (mode == 8 ? bench_seg2e<true> : (mode == 6 ? bench_seg4e : bench_seg2m))))));
+                                                       : (mode == 5 ? bench_seg2e<false> : (mode == 8 ? bench_seg2e<true> : (mode == 9 ? bench_seg2e<false, 10> : (mode == 6 ? bench_seg4e : bench_seg2m)))))));
   if (lds > 65536) (void)hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
   double *out;
   (void)hipMalloc(&out, grid * sizeof(double));
