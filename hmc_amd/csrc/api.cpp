@@ -319,6 +319,12 @@ int hmc_set_estep_windows(hmc_ctx *h, int mode, int window_loci) {
   return HMC_OK;
 }
 
+int hmc_last_collection_stats(const hmc_ctx *h, unsigned long long out[4]) {
+  if (!h || !out) return HMC_EARG;
+  for (int k = 0; k < 4; ++k) out[k] = h->c.gc_stats[k];
+  return HMC_OK;
+}
+
 int hmc_last_estep_windows(const hmc_ctx *h, int *windows, int *window_loci, int *groups, double *recompute_ms) {
   if (!h) return HMC_EARG;
   if (windows) *windows = h->c.last_windows;

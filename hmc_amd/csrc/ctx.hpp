@@ -1021,6 +1021,8 @@ struct Ctx {
   int last_windows = 0, last_window_loci = 0, last_window_groups = 0;  // hmc_last_estep_windows
   int n_restarts = 0;  // restarts of the last E-step (capacity growth, smaller windows): hmc_last_estep_restarts
   double ms_ck = 0;  // device ms of the trace collections (part of ms_s2)
+  DevBuf<unsigned long long> d_gc_stats;   // TraceGcArgs::stats
+  unsigned long long gc_stats[4] = {};     // of the last E-step (hmc_last_collection_stats)
   // Host wall time of the last EM iteration's phases (hmc_last_host_phases):
   // the E-step call, its store (re)allocation and end-order table build, the
   // sample gather after the passes, accept + HaploComp, the M-step call.

@@ -181,6 +181,7 @@ int Ctx::estep(double *ll_out, int *H_out, uint64_t *re_out) {
   ms_fwd = ms_tb = 0;
   ms_s1 = ms_s2 = ms_fb = ms_order = ms_ck = 0;
   last_windows = last_window_loci = last_window_groups = 0;
+  gc_stats[0] = gc_stats[1] = gc_stats[2] = gc_stats[3] = 0;
   n_fallback = n_order_redo = 0;
   n_struct_passes = n_value_passes = 0;
   int rc = 0;

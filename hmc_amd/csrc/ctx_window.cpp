@@ -58,6 +58,13 @@ int Ctx::estep_windowed(const std::vector<int32_t> &order) {
   std::vector<unsigned long long> rw, tw;  // exact needs per individual and window
   std::vector<int32_t> fw;                 // largest frontier per individual and window
 
+  // the collection left pending by collect_launch(): its statuses travel with
+  // the next structure pass's results (copied before that pass's sync,
+  // gc_check after it)
+  bool gc_pending = false;
+  std::vector<int32_t> gc_ids, gc_gs(n);  // the collection's individuals, their statuses
+  std::vector<std::pair<unsigned long long, int32_t>> gc_key;  // (trace words, position): the collection's order
+  std::function<int()> gc_check;
   bool bump = false;            // records from the store's bump allocator (the windows), else the regions rb / rs (the probe)
   // the structure pass's state capacity for the current window: twice the
   // largest frontier of the window before (its key table, HBM tier included,
@@ -129,11 +136,14 @@ int Ctx::estep_windowed(const std::vector<int32_t> &order) {
         (e2 = hipMemcpyAsync(ht.data(), d_tneed.p, (size_t)n * 8, hipMemcpyDeviceToHost, st)) ||
         (e2 = hipMemcpyAsync(hf.data(), d_fmax.p, (size_t)n * 4, hipMemcpyDeviceToHost, st)))
       return hipfail(e2, "windowed structure pass");
+    if (gc_pending && (e2 = hipMemcpyAsync(gc_gs.data(), d_gc_status.p, (size_t)n * 4, hipMemcpyDeviceToHost, st)))
+      return hipfail(e2, "trace collection");
     if ((rc2 = read_status({}, 0, false))) return rc2;
     hipEventElapsedTime(&ms, ev[0], ev[1]);
     ms_s1 += ms;
     if (!fwd) ms_ck += ms;
     ++n_struct_passes;
+    if (gc_pending && (rc2 = gc_check())) return rc2;
     if (debug_mem)
       fprintf(stderr, "[hmc] window %d/%d %s: structure pass %d individuals, %d x %d per CU, %.1f ms\n", w + 1, nwin,
               fwd ? "forward" : "recompute", np_, nw1, bpc1, ms);
@@ -241,7 +251,8 @@ int Ctx::estep_windowed(const std::vector<int32_t> &order) {
   const unsigned long long zero64 = 0;
   std::vector<unsigned long long> h_re_w(n), re_tot(n, 0);  // R_E per window (host sums: a pass can run twice)
   if ((e = d_ck_off.ensure((size_t)n * (nwin + 1))) || (e = d_ck_cursor.ensure(1)) || (e = d_bnd_off.ensure(n)) ||
-      (e = d_bnd_n.ensure(n)) || (e = d_node_cursor.ensure(1)) || (e = hipMemsetAsync(d_cost.p, 0, (size_t)n * 4, st)))
+      (e = d_bnd_n.ensure(n)) || (e = d_node_cursor.ensure(1)) || (e = d_gc_stats.ensure(4)) ||
+      (e = hipMemsetAsync(d_gc_stats.p, 0, 32, st)) || (e = hipMemsetAsync(d_cost.p, 0, (size_t)n * 4, st)))
     return hipfail(e, "windowed E-step alloc");
   rw.assign((size_t)n * nwin, 0);
   tw.assign((size_t)n * nwin, 0);
@@ -249,9 +260,6 @@ int Ctx::estep_windowed(const std::vector<int32_t> &order) {
   std::vector<int32_t> underflow;  // individuals whose likelihoods underflow: the classic passes (prune mode)
   // trace store: even windows fill it from the bottom, odd windows from the top
   uint64_t tr_lo = 0, tr_hi = 0;
-
-  bool gc_pending = false;
-  std::vector<int32_t> gc_ids;  // the collection's individuals
 
   // Value pass of window w over ids[0, k_) (trace regions in tbv).
   auto values = [&](int w, const int32_t *ids, int k_) -> int {
@@ -483,28 +491,48 @@ int Ctx::estep_windowed(const std::vector<int32_t> &order) {
 
   // Collection of window w - 1 (the survivors of every list entry at the end
   // of window w) over `grp`, after window w's value pass, a wavefront per
-  // individual.  (Run beside window w + 1's structure pass on a stream of its
-  // own it made that pass 50-60 % slower, more than the collection's own time:
-  // both are latency-bound on the same CUs.)  A node store that fills up is
-  // grown (contents kept) and the individuals that did not fit run again.
+  // individual, as many per CU as its LDS marks leave resident.  It stays
+  // pending: window w + 1's structure pass is enqueued behind it on the same
+  // stream and the host reads its statuses at that pass's sync, before the
+  // value pass that overwrites window w - 1's traces.  (Run beside that
+  // structure pass on a stream of its own it made the pass 50-60 % slower,
+  // more than the collection's own time: both are latency-bound on the same
+  // CUs.)  A node store that fills up is grown (contents kept) and the
+  // individuals that did not fit run again, to the end, before anything else.
   int gc_w = 0;
   auto collect_launch = [&](int w, const std::vector<int32_t> &grp) -> int {
     gc_w = w;
     const int lo0 = bound[w - 1], mid = bound[w], hi1 = bound[w + 1];
     uint64_t mwords = 0;
     int fb = 1;
+    double tsum = 0;
     for (int bi : grp) {
-      mwords = std::max<uint64_t>(mwords, (tw[(size_t)bi * nwin + w - 1] + tw[(size_t)bi * nwin + w]) / 32);
+      tsum += (double)(tw[(size_t)bi * nwin + w - 1] + tw[(size_t)bi * nwin + w]);
+      mwords = std::max<uint64_t>(mwords, tw[(size_t)bi * nwin + w - 1] / 32);  // bitmaps of [lo0, mid) only
       fb = std::max(fb, std::max(fw[(size_t)bi * nwin + w - 1], fw[(size_t)bi * nwin + w]));
     }
     if (grp.empty()) return HMC_OK;
     const int max_words = (int)(((uint64_t)fb * S + 31) / 32) + 1;
-    const size_t stride = (size_t)(hi1 - lo0 + 1) + 2 * (size_t)(max_words + 1) + mwords + (size_t)(hi1 - lo0) + 64;
-    const int grid = std::max(1, std::min((int)grp.size(), dev_cu * 16));  // a wavefront per individual
-    gc_ids = grp;  // heaviest collections first: the traces of the two windows
-    std::stable_sort(gc_ids.begin(), gc_ids.end(), [&](int32_t x, int32_t y) {
-      return tw[(size_t)x * nwin + w - 1] + tw[(size_t)x * nwin + w] > tw[(size_t)y * nwin + w - 1] + tw[(size_t)y * nwin + w];
+    // bitmap words of a locus at the mean frontier (trace_locus_words)
+    const double fmean_gc = std::max(1.0, (tsum / ((double)grp.size() * (hi1 - lo0)) - 2.0) / (1.0 + S));
+    const int lds_words = estep_trace_gc_lds_words(max_words, (int)std::min(1e9, fmean_gc * S / 32.0) + 1);
+    const size_t stride = estep_trace_gc_scratch_words(mid - lo0, max_words, mwords + 2 * (uint64_t)(mid - lo0) + 64);
+    // a wavefront per individual, every resident slot of the device, the
+    // scratch (sized by the heaviest individual's bitmaps) within 1/128 of the
+    // device's memory: cfg 3's E1 at 28 blocks per CU, 7 168 blocks, took 28-32
+    // ms per E-step in collections, at ~4 000-4 700 blocks in 2.4 GB 29 ms
+    const size_t scr_max = std::min<size_t>(SCRATCH_MAX, std::max<size_t>(totb / 128, (size_t)256 << 20));
+    const int grid = (int)std::max<size_t>(1, std::min<size_t>(std::min<size_t>(grp.size(), (size_t)dev_cu * estep_trace_gc_blocks_per_cu(lds_words)),
+                                                               scr_max / (stride * 4)));
+    // heaviest collections first: the traces of the two windows (ties in the order of `grp`)
+    gc_key.clear();
+    for (size_t q = 0; q < grp.size(); ++q)
+      gc_key.emplace_back(tw[(size_t)grp[q] * nwin + w - 1] + tw[(size_t)grp[q] * nwin + w], (int32_t)q);
+    std::sort(gc_key.begin(), gc_key.end(), [](const std::pair<unsigned long long, int32_t> &x, const std::pair<unsigned long long, int32_t> &y) {
+      return x.first != y.first ? x.first > y.first : x.second < y.second;
     });
+    gc_ids.resize(grp.size());
+    for (size_t q = 0; q < grp.size(); ++q) gc_ids[q] = grp[gc_key[q].second];
     hipError_t e2;
     if ((e2 = d_gc_scr.ensure(stride * grid)) || (e2 = d_gc_order.ensure(n)) || (e2 = d_gc_status.ensure(n)) ||
         (e2 = d_gc_nextq.ensure(1)) ||
@@ -526,39 +554,39 @@ int Ctx::estep_windowed(const std::vector<int32_t> &order) {
     g.scratch = d_gc_scr.p;
     g.scratch_stride = stride;
     g.max_words = max_words;
+    g.lds_words = lds_words;
     g.nodes = d_nodes.p;
     g.node_cap = d_nodes.n / 3;
     g.node_cursor = d_node_cursor.p;
     g.bnd_off = d_bnd_off.p;
     g.bnd_n = d_bnd_n.p;
     g.status = d_gc_status.p;
+    g.stats = d_gc_stats.p;
     hipEventRecord(ev[4], st);
-    if ((e2 = launch_estep_trace_gc(g, grid, st, 1))) return hipfail(e2, "estep_trace_gc launch");
+    if ((e2 = launch_estep_trace_gc(g, grid, st))) return hipfail(e2, "estep_trace_gc launch");
     hipEventRecord(ev[5], st);
     gc_pending = true;
     if (debug_mem)
-      fprintf(stderr, "[hmc] window %d/%d: collection of window %d for %zu individuals\n", w + 1, nwin, w, gc_ids.size());
+      fprintf(stderr, "[hmc] window %d/%d: collection of window %d for %zu individuals, %d blocks, %d LDS mark words, scratch %.2f GB\n", w + 1, nwin, w,
+              gc_ids.size(), grid, lds_words, stride * 4e-9 * grid);
     return HMC_OK;
   };
   std::function<int()> collect_finish;
-  collect_finish = [&]() -> int {
-    if (!gc_pending) return HMC_OK;
+  // the pending collection's statuses are in gc_gs and the stream has been synchronised since
+  gc_check = [&]() -> int {
     gc_pending = false;
     hipError_t e2;
-    std::vector<int32_t> gs(n);
-    if ((e2 = hipMemcpyAsync(gs.data(), d_gc_status.p, (size_t)n * 4, hipMemcpyDeviceToHost, st)) ||
-        (e2 = sync_st()))
-      return hipfail(e2, "trace collection");
-    hipEventElapsedTime(&ms, ev[4], ev[5]);
-    ms_ck += ms;
-    ms_s2 += ms;
+    float gms = 0;
+    hipEventElapsedTime(&gms, ev[4], ev[5]);
+    ms_ck += gms;
+    ms_s2 += gms;
     std::vector<int32_t> again;  // node store full: grown (contents kept), those individuals again
     for (int bi : gc_ids) {
-      if (gs[bi] == EST_GC_MISS) return fail(HMC_EHIP, "trace collection: a survivor's predecessor is missing (individual %d)", i0 + bi);
-      if (gs[bi] == EST_OVERFLOW_NODES) again.push_back(bi);
+      if (gc_gs[bi] == EST_GC_MISS) return fail(HMC_EHIP, "trace collection: a survivor's predecessor is missing (individual %d)", i0 + bi);
+      if (gc_gs[bi] == EST_OVERFLOW_NODES) again.push_back(bi);
     }
     if (debug_mem)
-      fprintf(stderr, "[hmc] collection for %zu individuals: %.1f ms%s\n", gc_ids.size(), ms, again.empty() ? "" : " (node store full: grows)");
+      fprintf(stderr, "[hmc] collection for %zu individuals: %.1f ms%s\n", gc_ids.size(), gms, again.empty() ? "" : " (node store full: grows)");
     if (!again.empty()) {
       unsigned long long used = 0;
       if ((e2 = hipMemcpyAsync(&used, d_node_cursor.p, 8, hipMemcpyDeviceToHost, st)) || (e2 = sync_st()))
@@ -572,6 +600,13 @@ int Ctx::estep_windowed(const std::vector<int32_t> &order) {
       return collect_finish();
     }
     return HMC_OK;
+  };
+  collect_finish = [&]() -> int {  // a pending collection to its end, with a sync of its own
+    if (!gc_pending) return HMC_OK;
+    hipError_t e2;
+    if ((e2 = hipMemcpyAsync(gc_gs.data(), d_gc_status.p, (size_t)n * 4, hipMemcpyDeviceToHost, st)) || (e2 = sync_st()))
+      return hipfail(e2, "trace collection");
+    return gc_check();
   };
 
   std::vector<unsigned long long> rec_all(n, 0);
@@ -594,8 +629,10 @@ int Ctx::estep_windowed(const std::vector<int32_t> &order) {
     tr_hi = d_trace.n;
     for (int w = 0; w < nwin; ++w) {
       if ((rc = window(w, grp))) return rc;
-      if (w >= 1 && w < nwin - 1 && ((rc = collect_launch(w, grp)) || (rc = collect_finish()))) return rc;
+      // (pending: finished at window w + 1's structure pass)
+      if (w >= 1 && w < nwin - 1 && (rc = collect_launch(w, grp))) return rc;
     }
+    if ((rc = collect_finish())) return rc;
     // the traceback: the last two windows' traces, then the survivors' chains
     if (!grp.empty()) {
       TracebackArgs t;
@@ -632,7 +669,8 @@ int Ctx::estep_windowed(const std::vector<int32_t> &order) {
       for (int w = 0; w < nwin; ++w) rec_all[bi] += rw[(size_t)bi * nwin + w];
     }
   }
-  if ((e = hipMemcpyAsync(d_re.p, re_tot.data(), (size_t)n * 8, hipMemcpyHostToDevice, st)) || (e = sync_st()))
+  if ((e = hipMemcpyAsync(d_re.p, re_tot.data(), (size_t)n * 8, hipMemcpyHostToDevice, st)) ||
+      (e = hipMemcpyAsync(gc_stats, d_gc_stats.p, 32, hipMemcpyDeviceToHost, st)) || (e = sync_st()))
     return hipfail(e, "windowed E-step");
   // individuals whose forward likelihoods underflow: the classic passes, which
   // rebuild their structure with extend()'s forward test (prune mode)

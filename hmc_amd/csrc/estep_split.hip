@@ -1949,83 +1949,150 @@ hipError_t launch_estep_structure2(const StructArgs &, int, int, hipStream_t) { 
 // HaploPair::getGenotype (HaploPair.cpp:91-124) only ever follows links from
 // the final candidates, and the k-best lists' links coalesce fast: on cfg 2's
 // E1 the ~1 000-2 300 list entries of the last locus reach ~10 entries 50 loci
-// back.  A block per individual marks, in one bitmap per locus (F x S bits),
-// the entries of [lo0, hi1) reachable from every entry at hi1 - 1, then writes
-// the marked entries of [lo0, mid) as nodes (ascending key per locus; the
-// predecessor's node by a prefix popcount of the locus below, or by a binary
-// search of the boundary list of the window before).
-constexpr uint32_t GC_LDS_WORDS = 1024;  // marks of loci up to 32 768 list entries in LDS (8 KB per block)
-template <int NW>
-__global__ __launch_bounds__(64 * NW) void estep_trace_gc(TraceGcArgs a) {
-  constexpr int NT = 64 * NW;
-  __shared__ unsigned long long red64[16];  // Blk<NW <= 4>: 2 NW + 8 ints, then NW u64 (8-byte aligned)
-  __shared__ int sq;
-  __shared__ uint32_t lmk[2][GC_LDS_WORDS];  // two loci's marks
-  const int tid = threadIdx.x, lane = lane_id(), wv = tid / WAVE;
-  const Blk<NW> B{(int *)red64, tid, lane, wv};
+// back.  A wavefront per individual walks [lo0, hi1) backward from every entry
+// at hi1 - 1.  The reached set of locus j - 1 is the image of locus j's under
+// the link map, so it never grows:
+//   dense   while it holds more than 64 entries it is a bitmap (F x S bits) in
+//           one of two LDS buffers (lds_words each; a larger locus marks in
+//           global scratch), copied to M for the loci of [lo0, mid);
+//   sparse  from the first locus with at most 64 entries on, one entry per
+//           lane in ascending order.  A step is one gather of link words, the
+//           predecessors' ranks among their distinct values (a readlane loop
+//           over the live lanes) and a redistribution through LDS: no bitmap,
+//           no scan, no atomic.  For the loci of [lo0, mid) each entry is
+//           stored as a finished node but for its position — the node words
+//           and the predecessor's item index — in reverse node order.
+// The survivors of [lo0, mid) become nodes, ascending key per locus: the sparse
+// loci's straight from their items, the dense loci above them by a prefix
+// popcount of the locus below; the predecessors of locus lo0 by a binary
+// search of the boundary list of the window before.
+// Locus metadata (trace offset, F) is loaded for 64 loci at a time, a lane per
+// locus, so a step's only dependent global access is the link gather.
+constexpr uint32_t GC_LDS_MAX = 7680;  // mark words per LDS buffer at most (two buffers within 64 KB)
+constexpr uint32_t GC_LIT = 1u << 31;  // item word 1: word 2 is the predecessor node itself (or NONE)
+
+__device__ inline uint32_t gc_rl(uint32_t v, int i) {
+  return (uint32_t)__builtin_amdgcn_readlane((int)v, __builtin_amdgcn_readfirstlane(i));
+}
+
+__device__ inline uint32_t wave_sum_u32(uint32_t x) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o);
+  return x;
+}
+__device__ inline unsigned long long wave_sum_u64(unsigned long long x) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o);
+  return x;
+}
+
+struct GcMeta {  // trace offset and F of the loci jb .. jb + 63, locus jb + lane in this lane
+  int jb = INT32_MIN;
+  unsigned long long off = 0;
+  uint32_t F = 0;
+};
+// (uniform call) locus j's trace offset and F; a batch that does not hold j
+// is reloaded to end at j (down) or to start at j
+__device__ inline void gc_meta(GcMeta &b, const TraceGcArgs &a, const unsigned long long *lo, int j, bool down,
+                               unsigned long long &off, uint32_t &F) {
+  if (b.jb == INT32_MIN || j < b.jb || j > b.jb + 63) {
+    b.jb = down ? j - 63 : j;
+    const int jj = b.jb + lane_id();
+    b.off = 0;
+    b.F = 0;
+    if (jj >= a.lo0 && jj < a.hi1) {
+      b.off = lo[jj];
+      b.F = a.trace[b.off];
+    }
+  }
+  const int i = j - b.jb;
+  off = (unsigned long long)gc_rl((uint32_t)(b.off >> 32), i) << 32 | gc_rl((uint32_t)b.off, i);
+  F = gc_rl(b.F, i);
+}
+
+size_t estep_trace_gc_scratch_words(int nold, int max_words, unsigned long long mwords) {
+  return ((size_t)nold + 2 * ((size_t)max_words + 1) + 192 * (size_t)nold + mwords + 3) & ~(size_t)3;
+}
+
+__global__ __launch_bounds__(64) void estep_trace_gc(TraceGcArgs a) {
+  extern __shared__ uint32_t gc_lds[];  // [64] list hand-over, then two mark buffers of lds_words
+  uint32_t *const lst = gc_lds;
+  const uint32_t W = (uint32_t)a.lds_words;
+  uint32_t *const lmk0 = gc_lds + 64, *const lmk1 = lmk0 + W;
+  const int lane = lane_id();
   const int S = a.S, L = a.L, hl = a.head_len;
-  const int nloc = a.hi1 - a.lo0;
-  uint32_t *moff = a.scratch + (size_t)blockIdx.x * a.scratch_stride;  // [nloc + 1]
-  uint32_t *preA = moff + nloc + 1, *preB = preA + a.max_words + 1;
-  uint32_t *M = preB + a.max_words + 1;
+  const int nold = a.mid - a.lo0;
+  uint32_t *const moff = a.scratch + (size_t)blockIdx.x * a.scratch_stride;  // [nold] bitmap offsets in M (dense loci)
+  uint32_t *const pre0 = moff + nold, *const pre1 = pre0 + a.max_words + 1;  // marks too large for LDS; prefix rows
+  uint32_t *const items = pre1 + a.max_words + 1;                         // [64 nold][3] sparse loci
+  uint32_t *const M = items + 192 * (size_t)nold;
   for (int q = blockIdx.x; q < a.n_order;) {
     const int bi = a.order[q];
     const unsigned long long *lo = a.loc_off + (size_t)bi * (L + 1);
-    auto words_at = [&](int j) -> uint32_t { return (a.trace[lo[j]] * (uint32_t)S + 31u) >> 5; };
-    // ---- bitmap offsets per locus
-    uint32_t acc = 0;
-    for (int c0 = 0; c0 < nloc; c0 += NT) {
-      const int c = c0 + tid;
-      const int w = c < nloc ? (int)words_at(a.lo0 + c) : 0;
-      int tot = 0;
-      const int ex = B.scan(w, &tot);
-      if (c < nloc) moff[c] = acc + (uint32_t)ex;
-      acc += (uint32_t)tot;
-    }
-    B.sync();
-    for (uint32_t w = tid; w < acc; w += NT) M[w] = 0u;
-    B.sync();
-    // ---- every list entry of the last locus, then backward along the links.
-    // A locus's marks live in one of two LDS buffers when they fit (LDS
-    // atomics instead of L2 atomics: the first loci back mark nearly every
-    // entry), else in its bitmap in M; marks of [lo0, mid) end up in M for
-    // the compaction below.
-    int cb = 0;  // the LDS buffer holding locus j's marks
+    GcMeta mb;
+    unsigned long long off;
+    uint32_t F;
+    int j = a.hi1 - 1;
+    gc_meta(mb, a, lo, j, true, off, F);
+    uint32_t cnt = 0, e = 0;  // sparse: the list length, this lane's entry (bit index t S + k)
+    bool sparse = false;
+    uint32_t macc = 0, dwords = 0;  // words of M taken; those of them of dense loci
+    int jsp = a.lo0 - 1;            // the highest locus in sparse form
+    // ---- every list entry of the last locus
     {
-      const int j = a.hi1 - 1;
-      const uint32_t F = a.trace[lo[j]];
-      const uint32_t *hdr = a.trace + lo[j] + 1;
-      const uint32_t nw = (F * (uint32_t)S + 31u) >> 5;
-      uint32_t *C = nw <= GC_LDS_WORDS ? lmk[cb] : M + moff[j - a.lo0];
-      for (uint32_t w = tid; w < nw; w += NT) {  // word by word: entries (t, k < nl(t))
-        uint32_t word = 0u;
-        uint32_t t = w * 32u / (uint32_t)S, k = w * 32u - t * (uint32_t)S;
-        uint32_t n = t < F ? (hdr[t] >> 16) & 0xFFu : 0u;
-        for (uint32_t i = 0; i < 32u; ++i) {
-          if (t < F && k < n) word |= 1u << i;
-          if (++k == (uint32_t)S) {
-            k = 0;
-            ++t;
-            n = t < F ? (hdr[t] >> 16) & 0xFFu : 0u;
-          }
+      const uint32_t *hdr = a.trace + off + 1;
+      uint32_t c = 0;
+      for (uint32_t t = lane; t < F; t += 64) c += (hdr[t] >> 16) & 0xFFu;
+      cnt = (uint32_t)wave_sum_u32(c);
+      if (cnt <= 64u) {
+        uint32_t pos = 0;
+        for (uint32_t t0 = 0; t0 < F; t0 += 64) {
+          const uint32_t t = t0 + lane;
+          const uint32_t n = t < F ? (hdr[t] >> 16) & 0xFFu : 0u;
+          const uint32_t incl = (uint32_t)wave_incl_scan((int)n);
+          for (uint32_t k = 0; k < n; ++k) lst[pos + incl - n + k] = t * (uint32_t)S + k;
+          pos += gc_rl(incl, 63);
         }
-        C[w] = word;
+        wsync();
+        e = (uint32_t)lane < cnt ? lst[lane] : 0u;
+        wsync();
+        sparse = true;
+        jsp = j;
+      } else {
+        const uint32_t nw = (F * (uint32_t)S + 31u) >> 5;
+        uint32_t *C = nw <= W ? lmk0 : pre0;
+        for (uint32_t w = lane; w < nw; w += 64) {  // word by word: entries (t, k < nl(t))
+          uint32_t word = 0u;
+          uint32_t t = w * 32u / (uint32_t)S, k = w * 32u - t * (uint32_t)S;
+          uint32_t n = t < F ? (hdr[t] >> 16) & 0xFFu : 0u;
+          for (uint32_t i = 0; i < 32u; ++i) {
+            if (t < F && k < n) word |= 1u << i;
+            if (++k == (uint32_t)S) {
+              k = 0;
+              ++t;
+              n = t < F ? (hdr[t] >> 16) & 0xFFu : 0u;
+            }
+          }
+          C[w] = word;
+        }
+        wsync();
       }
     }
-    B.sync();
-    for (int j = a.hi1 - 1; j > a.lo0; --j) {
-      const uint32_t F = a.trace[lo[j]];
-      const uint32_t *links = a.trace + trace_links(lo[j], F);
+    // ---- dense steps j -> j - 1
+    int cb = 0;  // the buffer holding locus j's marks
+    const int jd0 = j;
+    while (!sparse && j > a.lo0) {
+      const uint32_t *links = a.trace + trace_links(off, F);
       const uint32_t nw = (F * (uint32_t)S + 31u) >> 5;
-      const uint32_t nwp = (a.trace[lo[j - 1]] * (uint32_t)S + 31u) >> 5;
-      const uint32_t *Cj = nw <= GC_LDS_WORDS ? lmk[cb] : M + moff[j - a.lo0];
-      const bool pl = nwp <= GC_LDS_WORDS;
-      uint32_t *P = pl ? lmk[cb ^ 1] : M + moff[j - 1 - a.lo0];  // (M starts zeroed)
-      if (pl) {
-        for (uint32_t w = tid; w < nwp; w += NT) P[w] = 0u;
-        B.sync();
-      }
-      for (uint32_t w = tid; w < nw; w += NT)
+      unsigned long long offp;
+      uint32_t Fp;
+      gc_meta(mb, a, lo, j - 1, true, offp, Fp);
+      const uint32_t nwp = (Fp * (uint32_t)S + 31u) >> 5;
+      const uint32_t *Cj = nw <= W ? (cb ? lmk1 : lmk0) : (cb ? pre1 : pre0);
+      uint32_t *P = nwp <= W ? (cb ? lmk0 : lmk1) : (cb ? pre0 : pre1);
+      for (uint32_t w = lane; w < nwp; w += 64) P[w] = 0u;
+      wsync();
+      for (uint32_t w = lane; w < nw; w += 64)
         for (uint32_t b = Cj[w]; b; b &= b - 1u) {
           const uint32_t bit = w * 32u + (uint32_t)__builtin_ctz(b);
           const uint32_t m = links[bit];
@@ -2033,112 +2100,246 @@ __global__ __launch_bounds__(64 * NW) void estep_trace_gc(TraceGcArgs a) {
           const uint32_t pb = meta_pred(m) * (uint32_t)S + meta_idx(m);
           atomicOr(P + (pb >> 5), 1u << (pb & 31u));
         }
-      B.sync();
-      if (pl && j - 1 < a.mid) {  // the older window's marks, for the compaction
-        uint32_t *Mp = M + moff[j - 1 - a.lo0];
-        for (uint32_t w = tid; w < nwp; w += NT) Mp[w] = P[w];
-      }
+      wsync();
+      uint32_t c = 0;
+      for (uint32_t w = lane; w < nwp; w += 64) c += (uint32_t)__popc(P[w]);
+      cnt = (uint32_t)wave_sum_u32(c);
+      --j;
+      off = offp;
+      F = Fp;
       cb ^= 1;
+      if (j < a.mid) {  // the older window's marks, for the compaction
+        if (lane == 0) moff[j - a.lo0] = macc;
+        uint32_t *Mp = M + macc;
+        for (uint32_t w = lane; w < nwp; w += 64) Mp[w] = P[w];
+        if (cnt > 64u) macc += nwp;
+      }
+      if (cnt <= 64u) {  // sparse from here on
+        uint32_t pos = 0;
+        for (uint32_t c0 = 0; c0 < nwp; c0 += 64) {
+          const uint32_t w = c0 + lane;
+          uint32_t word = w < nwp ? P[w] : 0u;
+          const uint32_t n = (uint32_t)__popc(word);
+          const uint32_t incl = (uint32_t)wave_incl_scan((int)n);
+          uint32_t r = pos + incl - n;
+          for (; word; word &= word - 1u) lst[r++] = w * 32u + (uint32_t)__builtin_ctz(word);
+          pos += gc_rl(incl, 63);
+        }
+        wsync();
+        e = (uint32_t)lane < cnt ? lst[lane] : 0u;
+        wsync();
+        sparse = true;
+        jsp = j;
+      }
     }
-    B.sync();
+    dwords = macc;
+    const int js0 = j;
+    // ---- sparse steps: locus j's list in the lanes; its items when j < mid
+    const unsigned long long ob = a.bnd_off[bi];
+    const uint32_t on = a.lo0 > hl ? a.bnd_n[bi] : 0u;
+    uint32_t ppos = 0, cnt_top = 0;
+    bool have_top = false;
+    int miss = 0;
+    while (sparse && cnt > 0u) {
+      const bool live = (uint32_t)lane < cnt;
+      const bool old = j < a.mid;
+      uint32_t m = 1u << 31, h = 0u;
+      if (live) {
+        m = a.trace[trace_links(off, F) + e];
+        if (old) h = a.trace[off + 1 + e / (uint32_t)S];
+      }
+      const bool act = live && !meta_head(m);
+      const uint32_t pb = meta_pred(m) * (uint32_t)S + meta_idx(m);
+      uint32_t rank = 0, ncnt = 0;
+      bool dup = false;
+      if (j > a.lo0) {
+        // rank = distinct live predecessors below this lane's; dup = an earlier lane has the same
+        const unsigned long long am = __ballot(act);
+        for (unsigned long long mm = am; mm; mm &= mm - 1ull) {
+          const int i = __builtin_ctzll(mm);
+          const uint32_t v = gc_rl(pb, i);
+          const uint32_t di = gc_rl((uint32_t)dup, i);
+          rank += (!di && v < pb) ? 1u : 0u;
+          dup = dup || (v == pb && i < lane);
+        }
+        ncnt = (uint32_t)__popcll(__ballot(act && !dup));
+      }
+      if (old) {
+        if (!have_top) {
+          cnt_top = cnt;
+          have_top = true;
+        }
+        uint32_t w1 = (h & 0xFFFFu) | (meta_rev(m) ? 1u << 16 : 0u), w2 = NONE;
+        if (!act || j <= hl) {
+          w1 |= GC_LIT;
+        } else if (j > a.lo0) {
+          w2 = ppos + cnt + (ncnt - 1u - rank);  // the predecessor's item
+        } else {  // the window before: its boundary list, ascending keys
+          w1 |= GC_LIT;
+          const uint32_t key = meta_pred(m) << 8 | meta_idx(m);
+          uint32_t l0 = 0, l1 = on;
+          while (l0 < l1) {
+            const uint32_t md = (l0 + l1) >> 1;
+            if (a.nodes[3 * (ob + md)] < key) l0 = md + 1;
+            else l1 = md;
+          }
+          if (l0 < on && a.nodes[3 * (ob + l0)] == key) w2 = (uint32_t)(ob + l0);
+          else miss = 1;
+        }
+        if (live) {
+          const uint32_t t = e / (uint32_t)S, k = e - t * (uint32_t)S;
+          uint32_t *it = items + 3 * (size_t)(ppos + (cnt - 1u - (uint32_t)lane));
+          it[0] = t << 8 | k;
+          it[1] = w1;
+          it[2] = w2;
+        }
+        ppos += cnt;
+      }
+      if (j == a.lo0) break;
+      if (act && !dup) lst[rank] = pb;
+      wsync();
+      e = (uint32_t)lane < ncnt ? lst[lane] : 0u;
+      wsync();
+      cnt = ncnt;
+      --j;
+      gc_meta(mb, a, lo, j, true, off, F);
+    }
+    wsync();
     // ---- the survivors of [lo0, mid) as nodes
-    unsigned long long cnt = 0;
-    for (uint32_t w = tid; w < moff[a.mid - a.lo0]; w += NT) cnt += (unsigned long long)__popc(M[w]);
-    const unsigned long long total = B.reduce_u64(cnt);
+    const uint32_t T = ppos;
+    unsigned long long dn = 0;
+    for (uint32_t w = lane; w < dwords; w += 64) dn += (unsigned long long)__popc(M[w]);
+    const unsigned long long total = wave_sum_u64(dn) + T;
     unsigned long long base = 0;
-    if (tid == 0) {
+    if (lane == 0) {
       base = atomicAdd(a.node_cursor, total);
       if (base + total > a.node_cap) base = ~0ull;
     }
-    base = B.bcast64(base);
+    base = (unsigned long long)gc_rl((uint32_t)(base >> 32), 0) << 32 | gc_rl((uint32_t)base, 0);
     if (base == ~0ull) {
-      if (tid == 0) a.status[bi] = EST_OVERFLOW_NODES;
+      if (lane == 0) a.status[bi] = EST_OVERFLOW_NODES;
     } else {
-      const unsigned long long ob = a.bnd_off[bi];
-      const uint32_t on = a.lo0 > hl ? a.bnd_n[bi] : 0u;
-      unsigned long long nb = base, nb_prev = base;
-      uint32_t cnt_last = 0;
-      int miss = 0;
-      uint32_t *Pc = preA, *Pp = preB;
-      for (int j = a.lo0; j < a.mid; ++j) {
-        const uint32_t F = a.trace[lo[j]];
-        const uint32_t *hdr = a.trace + lo[j] + 1;
-        const uint32_t *links = a.trace + trace_links(lo[j], F);
-        const uint32_t *Mj = M + moff[j - a.lo0];
-        const uint32_t nw = (F * (uint32_t)S + 31u) >> 5;
-        uint32_t acc2 = 0;
-        for (uint32_t c0 = 0; c0 < nw; c0 += NT) {
-          const uint32_t w = c0 + tid;
-          const int v = w < nw ? __popc(Mj[w]) : 0;
-          int tot = 0;
-          const int ex = B.scan(v, &tot);
-          if (w < nw) Pc[w] = acc2 + (uint32_t)ex;
-          acc2 += (uint32_t)tot;
-        }
-        B.sync();
-        const uint32_t *Mp = j > a.lo0 ? M + moff[j - 1 - a.lo0] : nullptr;
-        for (uint32_t w = tid; w < nw; w += NT) {
-          unsigned long long r = nb + Pc[w];
-          for (uint32_t b = Mj[w]; b; b &= b - 1u) {
-            const uint32_t bit = w * 32u + (uint32_t)__builtin_ctz(b);
-            const uint32_t t = bit / (uint32_t)S, k = bit - t * (uint32_t)S;
-            const uint32_t m = links[bit];
-            uint32_t pred = NONE;
-            if (!meta_head(m) && j > hl) {
-              const uint32_t pt = meta_pred(m), pk = meta_idx(m);
-              if (j > a.lo0) {
-                const uint32_t pb = pt * (uint32_t)S + pk;
-                pred = (uint32_t)(nb_prev + Pp[pb >> 5] + (uint32_t)__popc(Mp[pb >> 5] & ((1u << (pb & 31u)) - 1u)));
-              } else {  // the window before: its boundary list, ascending keys
-                const uint32_t key = pt << 8 | pk;
-                uint32_t l0 = 0, l1 = on;
-                while (l0 < l1) {
-                  const uint32_t md = (l0 + l1) >> 1;
-                  if (a.nodes[3 * (ob + md)] < key) l0 = md + 1;
-                  else l1 = md;
-                }
-                if (l0 < on && a.nodes[3 * (ob + l0)] == key) pred = (uint32_t)(ob + l0);
-                else miss = 1;
-              }
-            }
-            uint32_t *nd = a.nodes + 3 * r;
-            nd[0] = t << 8 | k;
-            nd[1] = (hdr[t] & 0xFFFFu) | (meta_rev(m) ? 1u << 16 : 0u);
-            nd[2] = pred;
-            ++r;
-          }
-        }
-        nb_prev = nb;
-        nb += acc2;
-        cnt_last = acc2;
-        uint32_t *const tp_ = Pc;
-        Pc = Pp;
-        Pp = tp_;
-        B.sync();
+      for (uint32_t p = lane; p < T; p += 64) {  // items are in reverse node order
+        const uint32_t *it = items + 3 * (size_t)p;
+        const uint32_t w1 = it[1], w2 = it[2];
+        uint32_t *nd = a.nodes + 3 * (base + (T - 1u - p));
+        nd[0] = it[0];
+        nd[1] = w1 & ~GC_LIT;
+        nd[2] = (w1 & GC_LIT) ? w2 : (uint32_t)(base + (T - 1u - w2));
       }
-      miss = B.reduce_u64((unsigned long long)miss) != 0;
-      if (tid == 0) {
+      unsigned long long nb_prev = base + T - cnt_top;
+      uint32_t cnt_last = cnt_top;
+      if (jsp < a.mid - 1) {  // the dense loci above the sparse ones (the bitmap of locus jsp is in M)
+        unsigned long long nb = jsp >= a.lo0 ? nb_prev : base;
+        uint32_t *Pc = pre0, *Pp = pre1;
+        GcMeta cm;
+        for (int jc = jsp >= a.lo0 ? jsp : a.lo0; jc < a.mid; ++jc) {
+          const bool emit = jc > jsp;
+          gc_meta(cm, a, lo, jc, false, off, F);
+          const uint32_t *hdr = a.trace + off + 1;
+          const uint32_t *links = a.trace + trace_links(off, F);
+          const uint32_t *Mj = M + moff[jc - a.lo0];
+          const uint32_t nw = (F * (uint32_t)S + 31u) >> 5;
+          uint32_t acc2 = 0;
+          for (uint32_t c0 = 0; c0 < nw; c0 += 64) {
+            const uint32_t w = c0 + lane;
+            const uint32_t v = w < nw ? (uint32_t)__popc(Mj[w]) : 0u;
+            const uint32_t incl = (uint32_t)wave_incl_scan((int)v);
+            if (w < nw) Pc[w] = acc2 + incl - v;
+            acc2 += gc_rl(incl, 63);
+          }
+          wsync();
+          const uint32_t *Mp = jc > a.lo0 ? M + moff[jc - 1 - a.lo0] : nullptr;
+          for (uint32_t w = lane; emit && w < nw; w += 64) {
+            unsigned long long r = nb + Pc[w];
+            for (uint32_t b = Mj[w]; b; b &= b - 1u) {
+              const uint32_t bit = w * 32u + (uint32_t)__builtin_ctz(b);
+              const uint32_t t = bit / (uint32_t)S, k = bit - t * (uint32_t)S;
+              const uint32_t m = links[bit];
+              uint32_t pred = NONE;
+              if (!meta_head(m) && jc > hl) {
+                const uint32_t pt = meta_pred(m), pk = meta_idx(m);
+                if (jc > a.lo0) {
+                  const uint32_t pb = pt * (uint32_t)S + pk;
+                  pred = (uint32_t)(nb_prev + Pp[pb >> 5] + (uint32_t)__popc(Mp[pb >> 5] & ((1u << (pb & 31u)) - 1u)));
+                } else {  // the window before: its boundary list, ascending keys
+                  const uint32_t key = pt << 8 | pk;
+                  uint32_t l0 = 0, l1 = on;
+                  while (l0 < l1) {
+                    const uint32_t md = (l0 + l1) >> 1;
+                    if (a.nodes[3 * (ob + md)] < key) l0 = md + 1;
+                    else l1 = md;
+                  }
+                  if (l0 < on && a.nodes[3 * (ob + l0)] == key) pred = (uint32_t)(ob + l0);
+                  else miss = 1;
+                }
+              }
+              uint32_t *nd = a.nodes + 3 * r;
+              nd[0] = t << 8 | k;
+              nd[1] = (hdr[t] & 0xFFFFu) | (meta_rev(m) ? 1u << 16 : 0u);
+              nd[2] = pred;
+              ++r;
+            }
+          }
+          nb_prev = nb;
+          nb += acc2;
+          cnt_last = acc2;
+          uint32_t *const tp_ = Pc;
+          Pc = Pp;
+          Pp = tp_;
+          wsync();
+        }
+      }
+      miss = __ballot(miss != 0) != 0ull;
+      if (lane == 0) {
         a.bnd_off[bi] = nb_prev;
         a.bnd_n[bi] = cnt_last;
         if (miss) a.status[bi] = EST_GC_MISS;
       }
     }
-    B.sync();
-    if (tid == 0) sq = atomicAdd(a.next_q, 1) + (int)gridDim.x;
-    B.sync();
-    q = sq;
+    wsync();
+    if (a.stats && lane == 0) {  // steps taken dense / sparse, dense loci written, switches inside [lo0, mid - 1)
+      atomicAdd(a.stats + 0, (unsigned long long)(jd0 - js0));
+      atomicAdd(a.stats + 1, (unsigned long long)(js0 - j));
+      atomicAdd(a.stats + 2, (unsigned long long)(jsp < a.mid - 1 ? a.mid - 1 - (jsp >= a.lo0 ? jsp : a.lo0 - 1) : 0));
+      atomicAdd(a.stats + 3, (unsigned long long)(jsp >= a.lo0 && jsp < a.mid - 1 ? 1 : 0));
+    }
+    int nq = 0;
+    if (lane == 0) nq = atomicAdd(a.next_q, 1) + (int)gridDim.x;
+    q = (int)gc_rl((uint32_t)nq, 0);
   }
 }
 
-hipError_t launch_estep_trace_gc(const TraceGcArgs &a, int grid, hipStream_t st, int nw) {
+static size_t gc_lds_bytes(int lds_words) { return (64 + 2 * (size_t)lds_words) * 4; }
+
+// Marks in LDS for the loci of up to twice the typical bitmap (at least 608
+// words: two buffers of a block within 1/32 of a CU's LDS); the few larger
+// loci mark in global scratch.  (Sized for the largest locus — cfg 3's E1:
+// 2 761-3 830 words against a mean of ~135 — the buffers left 5-7 blocks per
+// CU resident.)
+int estep_trace_gc_lds_words(int max_words, int typ_words) {
+  const int64_t want = std::max<int64_t>(608, 2 * (int64_t)typ_words);
+  return (int)std::min<int64_t>(std::min<int64_t>(std::max(max_words, 1), want), GC_LDS_MAX);
+}
+
+int estep_trace_gc_blocks_per_cu(int lds_words) {
+  int nb = 0;
+  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, estep_trace_gc, 64, gc_lds_bytes(lds_words)) != hipSuccess || nb < 1) {
+    (void)hipGetLastError();
+    nb = 1;
+  }
+  return nb;
+}
+
+hipError_t launch_estep_trace_gc(const TraceGcArgs &a, int grid, hipStream_t st) {
   if (a.n_order <= 0) return hipSuccess;
   if (a.S < 1 || a.S > S_MAX || a.lo0 < a.head_len || a.mid <= a.lo0 || a.hi1 <= a.mid || a.hi1 > a.L + 1 || grid < 1 ||
-      (nw != 1 && nw != 4))
+      a.lds_words < 1 || a.lds_words > (int)GC_LDS_MAX || a.max_words < 1 ||
+      a.scratch_stride < estep_trace_gc_scratch_words(a.mid - a.lo0, a.max_words, 0))
     return hipErrorInvalidValue;
-  // nw = 1: a wavefront per individual — the marking walks the loci one after
-  // another, so more individuals in flight hide its latency
-  if (nw == 4) hipLaunchKernelGGL(estep_trace_gc<4>, dim3(grid), dim3(256), 0, st, a);
-  else hipLaunchKernelGGL(estep_trace_gc<1>, dim3(grid), dim3(64), 0, st, a);
+  // a wavefront per individual — the walk takes the loci one after another, so
+  // the individuals in flight hide its latency
+  hipLaunchKernelGGL(estep_trace_gc, dim3(grid), dim3(64), gc_lds_bytes(a.lds_words), st, a);
   return hipGetLastError();
 }
 

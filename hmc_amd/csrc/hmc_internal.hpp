@@ -322,17 +322,29 @@ struct TraceGcArgs {
   const uint32_t *trace = nullptr;
   const unsigned long long *loc_off = nullptr;
   int lo0 = 0, mid = 0, hi1 = 0;
-  uint32_t *scratch = nullptr;  // per block: mark offsets, two prefix rows, the reached-entry bitmaps
+  uint32_t *scratch = nullptr;  // per block: estep_trace_gc_scratch_words()
   size_t scratch_stride = 0;    // words
   int max_words = 1;            // bitmap words of the largest locus (F x S bits)
+  int lds_words = 1;            // words of each of the two LDS mark buffers (estep_trace_gc_lds_words)
   uint32_t *nodes = nullptr;
   unsigned long long node_cap = 0;       // nodes
   unsigned long long *node_cursor = nullptr;
   unsigned long long *bnd_off = nullptr;  // [batch]
   uint32_t *bnd_n = nullptr;              // [batch]
   int32_t *status = nullptr;              // EST_OVERFLOW_NODES: the node store is full (nothing changed)
+  // added to per individual, or null: loci stepped over as a bitmap / as a
+  // list, loci of [lo0, mid) written from bitmaps, individuals that went from
+  // bitmap to list inside [lo0, mid - 1)
+  unsigned long long *stats = nullptr;
 };
-hipError_t launch_estep_trace_gc(const TraceGcArgs &a, int grid, hipStream_t st, int nw = 1);
+// Scratch words per block: bitmap offsets and 64 items of 3 words per locus of
+// [lo0, mid) (nold loci), two rows of max_words + 1, and mwords bitmap words
+// (at least the sum of the F x S bitmaps of [lo0, mid)).
+size_t estep_trace_gc_scratch_words(int nold, int max_words, unsigned long long mwords);
+// words of an LDS mark buffer: loci of up to max_words bitmap words, typ_words the typical locus
+int estep_trace_gc_lds_words(int max_words, int typ_words);
+int estep_trace_gc_blocks_per_cu(int lds_words);  // resident blocks (one wavefront each) per CU
+hipError_t launch_estep_trace_gc(const TraceGcArgs &a, int grid, hipStream_t st);
 
 size_t estep_scratch_bytes(int fcap, int hcap, int S, int nw);
 size_t estep_lds_bytes(int S, int fc, int hc, int nw, int amax);

@@ -276,6 +276,12 @@ class HaploModel:
         return dict(windows=w.value, window_loci=wl.value, groups=g.value, collection_ms=ms.value,
                     restarts=rs.value, window_scale=sc.value)
 
+    def collection_stats(self) -> dict:
+        """The last E-step's trace collections (hmc_last_collection_stats)."""
+        out = (C.c_uint64 * 4)()
+        self._check(lib().hmc_last_collection_stats(self._h, out))
+        return dict(dense_steps=out[0], sparse_steps=out[1], dense_loci_written=out[2], switches_in_window=out[3])
+
     HOST_PHASES = ("estep", "stores", "gmodel", "samples", "accept", "haplocomp", "mstep", "estep_setup")
 
     def host_phases(self) -> dict:

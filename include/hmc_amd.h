@@ -438,6 +438,12 @@ int hmc_set_estep_windows(hmc_ctx *ctx, int mode, int window_loci);
  * individuals, and device ms of the trace collections (part of the value
  * passes' time). */
 int hmc_last_estep_windows(const hmc_ctx *ctx, int *windows, int *window_loci, int *groups, double *recompute_ms);
+/* The last E-step's trace collections, summed over individuals and windows:
+ * out[0] loci stepped over with the reached entries as a bitmap, out[1] as a
+ * list of at most 64 entries, out[2] loci of the collected windows written
+ * from bitmaps, out[3] individuals-and-windows that went from bitmap to list
+ * inside the collected window.  All 0 for the classic passes. */
+int hmc_last_collection_stats(const hmc_ctx *ctx, unsigned long long out[4]);
 /* Restarts of the last E-step (a frontier or contribution capacity grown, or
  * a window's traces past the store: windows 0.6x as long, or for a fixed
  * window length smaller groups) and the window scale now in force (1.0 until
