@@ -875,6 +875,35 @@ int hmc_get_resolutions(hmc_ctx *h, int32_t *out) {
   return HMC_OK;
 }
 
+int hmc_genotype_posteriors(hmc_ctx *h, int64_t *n_sites, int *n_pairs, int32_t *indiv, int32_t *locus, int32_t *status,
+                            double *post) {
+  if (!h) return HMC_EARG;
+  Ctx &c = h->c;
+  if (!c.have_panel) return c.fail(HMC_EARG, "no panel loaded");
+  if (n_pairs) *n_pairs = c.pan.amax * (c.pan.amax + 1) / 2;
+  if (!indiv && !locus && !status && !post) {  // count only: no device work
+    Ctx::SiteList sl;
+    c.site_list(sl);
+    if (n_sites) *n_sites = (int64_t)sl.locus.size();
+    return HMC_OK;
+  }
+  const int rc = c.site_posteriors(indiv, locus, status, post);
+  if (rc) return rc;
+  if (n_sites) *n_sites = (int64_t)c.n_sites_last;
+  return HMC_OK;
+}
+
+int hmc_last_posterior_stats(const hmc_ctx *h, double *structure_ms, double *fb_ms, double *sites_ms, int *groups,
+                             int *n_pruned) {
+  if (!h) return HMC_EARG;
+  if (structure_ms) *structure_ms = h->c.xp_ms_struct;
+  if (fb_ms) *fb_ms = h->c.xp_ms_fb;
+  if (sites_ms) *sites_ms = h->c.xp_ms_sites;
+  if (groups) *groups = h->c.xp_groups;
+  if (n_pruned) *n_pruned = h->c.xp_pruned;
+  return HMC_OK;
+}
+
 int hmc_run(hmc_ctx *h, int max_iteration, hmc_iter_log *log, int log_cap, int *iterations, double *t_m0_s,
             uint64_t *r_m0, int *n_patterns0) {
   if (!h) return HMC_EARG;
@@ -943,6 +972,44 @@ int hmc_write_phase(hmc_ctx *h, const char *path) {
     }
   }
   fclose(fp);
+  return HMC_OK;
+}
+
+int hmc_write_posteriors(hmc_ctx *h, const char *path) {
+  if (!h || !path || !h->c.have_panel) return HMC_EARG;
+  Ctx &c = h->c;
+  Ctx::SiteList sl;
+  c.site_list(sl);
+  const size_t ns = sl.locus.size();
+  const int NP = c.pan.amax * (c.pan.amax + 1) / 2;
+  std::vector<int32_t> indiv(ns), locus(ns), status(ns);
+  std::vector<double> post(ns * NP);
+  int rc;
+  if ((rc = c.site_posteriors(indiv.data(), locus.data(), status.data(), post.data(), &sl))) return rc;
+  FILE *fp = fopen(path, "w");
+  if (!fp) return c.fail(HMC_EIO, "Can not open file %s!", path);
+  const hmc::FileData d = writer_meta(c);
+  fprintf(fp, "Id\tMarker\tAlleleLo\tAlleleHi\tPosterior\n");
+  auto put_symbol = [&](int k, int j) {  // as the genotype files spell alleles: characters ('S') or integers ('M')
+    const int32_t a = c.pan.symbol(k, (uint8_t)j);
+    if (c.pan.types[k] == 'S') fprintf(fp, "\t%c", (char)a);
+    else fprintf(fp, "\t%d", a);
+  };
+  for (size_t q = 0; q < ns; ++q) {
+    const double *row = post.data() + q * NP;
+    int b = 0;
+    for (int hi = 0; hi < c.pan.amax; ++hi)
+      for (int lo = 0; lo <= hi; ++lo, ++b) {
+        if (!(row[b] != 0.0)) continue;
+        fprintf(fp, "%s\t%s", d.ids[indiv[q]].c_str(), d.names[locus[q]].c_str());
+        put_symbol(locus[q], lo);
+        put_symbol(locus[q], hi);
+        fprintf(fp, "\t%.17g\n", row[b]);
+      }
+  }
+  // a write that failed anywhere (a full disk) leaves the stream's error flag set, or fails the close
+  const bool bad = ferror(fp) != 0;
+  if (fclose(fp) != 0 || bad) return c.fail(HMC_EIO, "Can not write file %s!", path);
   return HMC_OK;
 }
 

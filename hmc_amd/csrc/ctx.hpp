@@ -401,6 +401,7 @@ struct Ctx {
   std::vector<int32_t> h_rowmap;                        // dense sample h -> slot row
   std::vector<unsigned long long> h_re;
   bool have_estep = false;
+  uint64_t estep_gen = ~0ull;  // model_gen of the table the last E-step ran on (d_total belongs to it)
   std::vector<uint8_t> best_res;  // [n][2][L] accepted resolutions (allele index), host copy
   bool have_best = false;
   bool best_on_host = false;      // best_res matches d_best
@@ -793,6 +794,28 @@ struct Ctx {
 
   // exact_fb + exact_walk over the group d_order2[0, k) (structure records in place)
   int exact_group(const int32_t *ids, int k, const std::function<int(std::vector<int32_t> &)> &rerun = nullptr);
+  // Genotype posteriors at missing loci (hmc_genotype_posteriors): the
+  // individuals of the shard through estep_split(order, true) like a round of
+  // the exact M-step, with exact_site_posteriors per group in place of the
+  // trie walk (xp_mode).  Sites: (individual, locus) with a missing input
+  // allele, individual-major, loci ascending; rows are shard-local.
+  struct SiteList {
+    std::vector<unsigned long long> off;  // [n + 1] over the shard's individuals
+    std::vector<int32_t> locus;
+  };
+  // (pre: the shard's site list when the caller has built it already)
+  int site_posteriors(int32_t *indiv, int32_t *locus, int32_t *status, double *post, const SiteList *pre = nullptr);
+  void site_list(SiteList &sl) const;
+  int site_group(const ExactArgs &x, int k, int dev_cu);
+  bool xp_mode = false;
+  DevBuf<unsigned long long> d_site_off;
+  DevBuf<int32_t> d_site_locus, d_site_status;
+  DevBuf<double> d_site_post;
+  // of the last call: device ms of the structure passes, exact_fb and the site
+  // kernel, groups, individuals on pruned records
+  double xp_ms_struct = 0, xp_ms_fb = 0, xp_ms_sites = 0;
+  int xp_groups = 0, xp_pruned = 0;
+  size_t n_sites_last = 0;
   // The trie walk of one group (the current round's trie).
   int exact_walk_group(ExactArgs &x, int k, int dev_cu);
   // Breadth-first (default): work units of one trie node each, lane by lane

@@ -241,6 +241,7 @@ int Ctx::estep(double *ll_out, int *H_out, uint64_t *re_out) {
   for (int i = 0; i < n; ++i) re += h_re[i];
   have_samples = true;
   have_estep = true;
+  estep_gen = model_gen;
   if (ll_out) *ll_out = ll;
   if (H_out) *H_out = H;
   if (re_out) *re_out = re;

@@ -204,13 +204,20 @@ int Ctx::exact_group(const int32_t *ids, int k, const std::function<int(std::vec
     x.fmax = xc_fmax;
     return exact_walk_group(x, k, dev_cu);
   }
+  if (xp_mode) hipEventRecord(ev[0], st);
   if ((e = launch_exact_fb(x, std::max(1, std::min(k, dev_cu * 8)), st))) return hipfail(e, "exact_fb");
+  if (xp_mode) hipEventRecord(ev[1], st);
   const int n = nloc();
   std::vector<int32_t> xs(n), fm(n);
   if ((e = hipMemcpyAsync(xs.data(), d_xstatus.p, (size_t)n * 4, hipMemcpyDeviceToHost, st)) ||
       (e = hipMemcpyAsync(fm.data(), d_xfmax.p, (size_t)n * 4, hipMemcpyDeviceToHost, st)) ||
       (e = sync_st()))
     return hipfail(e, "exact_fb");
+  auto fb_timed = [&]() {  // (posteriors only; the stream is drained at both call sites)
+    float ms = 0;
+    if (xp_mode && hipEventElapsedTime(&ms, ev[0], ev[1]) == hipSuccess) xp_ms_fb += ms;
+  };
+  fb_timed();
   std::vector<int32_t> redo;
   for (int q = 0; q < k; ++q)
     if (xs[ids[q]] == EST_NEEDS_EXACT) redo.push_back(ids[q]);
@@ -225,11 +232,14 @@ int Ctx::exact_group(const int32_t *ids, int k, const std::function<int(std::vec
     ExactArgs x2 = x;
     x2.order = d_redo.p;
     x2.n_order = nr;
+    if (xp_mode) hipEventRecord(ev[0], st);
     if ((e = launch_exact_fb(x2, std::max(1, std::min(nr, dev_cu * 8)), st))) return hipfail(e, "exact_fb");
+    if (xp_mode) hipEventRecord(ev[1], st);
     if ((e = hipMemcpyAsync(xs.data(), d_xstatus.p, (size_t)n * 4, hipMemcpyDeviceToHost, st)) ||
         (e = hipMemcpyAsync(fm.data(), d_xfmax.p, (size_t)n * 4, hipMemcpyDeviceToHost, st)) ||
         (e = sync_st()))
       return hipfail(e, "exact_fb");
+    fb_timed();
     for (int r : redo)
       if (xs[r] == EST_NEEDS_EXACT) return fail(HMC_EHIP, "exact M-step: pruned records still underflow (individual %d)", i0 + r);
   }
@@ -239,7 +249,121 @@ int Ctx::exact_group(const int32_t *ids, int k, const std::function<int(std::vec
   xc_fmax = fmax;
   xc_k = k;
   ++xc_groups;
+  if (xp_mode) return site_group(x, k, dev_cu);  // genotype posteriors: no trie, no walk
   return exact_walk_group(x, k, dev_cu);
+}
+
+int Ctx::site_group(const ExactArgs &x, int k, int dev_cu) {
+  SiteArgs s;
+  s.site_off = d_site_off.p;
+  s.site_locus = d_site_locus.p;
+  s.post = d_site_post.p;
+  s.site_status = d_site_status.p;
+  s.n_pairs = pan.amax * (pan.amax + 1) / 2;
+  hipError_t e;
+  hipEventRecord(ev[0], st);
+  if ((e = launch_exact_site_posteriors(x, s, std::max(1, std::min(k, dev_cu * 8)), st))) return hipfail(e, "exact_site_posteriors");
+  hipEventRecord(ev[1], st);
+  if ((e = sync_st())) return hipfail(e, "exact_site_posteriors");
+  float ms = 0;
+  hipEventElapsedTime(&ms, ev[0], ev[1]);
+  xp_ms_sites += ms;
+  return HMC_OK;
+}
+
+void Ctx::site_list(SiteList &sl) const {
+  std::vector<unsigned long long> &off = sl.off;
+  std::vector<int32_t> &locus = sl.locus;
+  const int n = nloc(), L = pan.L;
+  off.assign((size_t)n + 1, 0);
+  locus.clear();
+  for (int i = 0; i < n; ++i) {
+    const uint8_t *g0 = pan.idx.data() + ((size_t)(i0 + i) * 2) * L, *g1 = g0 + L;
+    for (int k = 0; k < L; ++k)
+      if (g0[k] == MISSING || g1[k] == MISSING) locus.push_back(k);
+    off[i + 1] = locus.size();
+  }
+}
+
+int Ctx::site_posteriors(int32_t *indiv, int32_t *locus, int32_t *status, double *post, const SiteList *pre) {
+  if (!have_estep) return fail(HMC_EARG, "genotype posteriors need an E-step first (hmc_resolve_all)");
+  // P(genotype) of the last E-step is the divisor: the table must still be the one it ran on
+  if (estep_gen != model_gen)
+    return fail(HMC_EARG, "genotype posteriors: the model changed since the last E-step (hmc_resolve_all again)");
+  if (pan.amax > 44)  // the records pack a locus's allele pairs (amax (amax + 1) / 2) in 10 bits
+    return fail(HMC_EUNSUPPORTED, "genotype posteriors with more than 44 alleles per locus");
+  const int n = nloc(), NP = pan.amax * (pan.amax + 1) / 2;
+  SiteList own;
+  if (!pre) site_list(own);
+  const std::vector<unsigned long long> &off = pre ? pre->off : own.off;
+  const std::vector<int32_t> &loc = pre ? pre->locus : own.locus;
+  const size_t ns = loc.size();
+  n_sites_last = ns;
+  xp_ms_struct = xp_ms_fb = xp_ms_sites = 0;
+  xp_groups = xp_pruned = 0;
+  if (indiv)
+    for (int i = 0; i < n; ++i)
+      for (unsigned long long q = off[i]; q < off[i + 1]; ++q) indiv[q] = i0 + i;
+  if (locus && ns) std::copy(loc.begin(), loc.end(), locus);
+  if (ns == 0) return HMC_OK;
+  hipError_t er;
+  if ((er = d_site_off.ensure((size_t)n + 1)) || (er = d_site_locus.ensure(ns)) || (er = d_site_status.ensure(ns)) ||
+      (er = d_site_post.ensure(ns * NP)) || (er = d_xstatus.ensure(n)) || (er = d_xre.ensure(n)) || (er = d_xfmax.ensure(n)) ||
+      (er = hipMemcpyAsync(d_site_off.p, off.data(), ((size_t)n + 1) * 8, hipMemcpyHostToDevice, st)) ||
+      (er = hipMemcpyAsync(d_site_locus.p, loc.data(), ns * 4, hipMemcpyHostToDevice, st)) ||
+      (er = hipMemsetAsync(d_site_post.p, 0, ns * NP * 8, st)) || (er = hipMemsetAsync(d_site_status.p, 0, ns * 4, st)))
+    return hipfail(er, "posteriors");
+  // What the exact-mode structure pass shares with the E-step and a later call
+  // can see is put back afterwards: the last E-step's pass times and counts,
+  // its per-individual status (hmc_get_estep), the frontier statistic and the
+  // structure stamps, and the capacities a restart may have grown.  The stores
+  // (records, traces) are dead between an E-step and the next M- or E-step.
+  const double s1_0 = ms_s1, fb_0 = ms_fb;
+  const int passes_0 = n_struct_passes, pruned_0 = exact_pruned, fcap_0 = fcap, ccap_0 = ccap_mult;
+  const uint64_t rec_words_0 = rec_words;
+  const std::vector<int32_t> status_0 = h_status;
+  uint32_t maxst_0 = 0;
+  unsigned long long stamps_0[20] = {};
+  if ((er = hipMemcpyAsync(&maxst_0, d_maxst.p, 4, hipMemcpyDeviceToHost, st)) ||
+      (er = hipMemcpyAsync(stamps_0, d_stamps.p + 20, sizeof stamps_0, hipMemcpyDeviceToHost, st)) || (er = sync_st()))
+    return hipfail(er, "posteriors");
+  std::vector<int32_t> order(n);
+  for (int q = 0; q < n; ++q) order[q] = q;
+  std::stable_sort(order.begin(), order.end(), [&](int x, int y) { return h_cost[x] > h_cost[y]; });
+  // The records of a cached exact M-step group are overwritten here, and the
+  // posteriors' own group must never be taken for one: no reuse on either side.
+  xc_reuse = false;
+  xp_mode = true;
+  exact_pruned = 0;
+  ms_s1 = ms_fb = 0;
+  int rc;
+  while (true) {  // a capacity overflow restarts the pass; every site is written again
+    xc_groups = 0;
+    xp_ms_fb = xp_ms_sites = 0;
+    rc = estep_split(order, true);
+    if (rc != ESTEP_RESTART) break;
+  }
+  xp_mode = false;
+  xc_reuse = false;
+  xp_ms_struct = ms_s1 + ms_fb;  // (ms_fb: the pruned structure re-runs of underflowing individuals)
+  xp_groups = xc_groups;
+  xp_pruned = exact_pruned;
+  ms_s1 = s1_0;
+  ms_fb = fb_0;
+  n_struct_passes = passes_0;
+  exact_pruned = pruned_0;
+  fcap = fcap_0;
+  ccap_mult = ccap_0;
+  rec_words = rec_words_0;
+  h_status = status_0;
+  if ((er = hipMemcpyAsync(d_maxst.p, &maxst_0, 4, hipMemcpyHostToDevice, st)) ||
+      (er = hipMemcpyAsync(d_stamps.p + 20, stamps_0, sizeof stamps_0, hipMemcpyHostToDevice, st)) || (er = sync_st()))
+    return rc ? rc : hipfail(er, "posteriors");
+  if (rc) return rc;
+  if ((status && (er = hipMemcpyAsync(status, d_site_status.p, ns * 4, hipMemcpyDeviceToHost, st))) ||
+      (post && (er = hipMemcpyAsync(post, d_site_post.p, ns * NP * 8, hipMemcpyDeviceToHost, st))) || (er = sync_st()))
+    return hipfail(er, "posteriors");
+  return HMC_OK;
 }
 
 int Ctx::exact_walk_group(ExactArgs &x, int k, int dev_cu) {

@@ -967,4 +967,101 @@ hipError_t launch_exact_walk(const ExactArgs &a, int grid, hipStream_t st, int i
   return hipGetLastError();
 }
 
+// Posterior of the unordered allele pair at every site (individual, locus with
+// a missing input allele) of the group, from the forward and backward
+// likelihoods exact_fb left in the x-store: the states after locus k + 1
+// (record k + 1) carry the pair of alleles at locus k in their header word,
+// sum over a locus's states of fwd * bwd is P(genotype), so the bin of {x, y}
+// is the sum over the states that carry {x, y}, over P(genotype).  Loci before
+// the last head locus read the head record and take their alleles from the
+// states' two head patterns, as exact_walk does.
+// One block per individual; a wavefront owns a whole bin: lane l adds the
+// products of the bin's states l, l + 64, ... in ascending order, then the 64
+// lanes are summed by the fixed butterfly (group_sum_fixed).  The order of a
+// bin's sum depends on the record's state order alone, so every block size,
+// grid, grouping and shard gives the same bits; no floating-point atomics.
+// States of other bins (and bins no state carries) add +0.0.  With more bins
+// than waves (three or more alleles) one scan of the record first marks the
+// bins that some state carries in an LDS bitmap (integer or: order-free), and
+// only those are summed — at most the pairs the genotype allows, a handful at
+// a site with one known allele, instead of all A (A + 1) / 2; the others are
+// the 0.0 their sum of zeros would give.
+// An individual whose P(genotype) is subnormal (below DBL_MIN: thousands of
+// loci) has lost the bits of its likelihoods — exact_fb and the value pass
+// keep raw doubles — so its rows would not sum to 1: they are zeros with
+// site status 2.
+__global__ __launch_bounds__(1024) void exact_site_posteriors(ExactArgs a, SiteArgs s) {
+  const int lane = threadIdx.x & (WAVE - 1), wave = threadIdx.x / WAVE, nw = blockDim.x / WAVE;
+  const int L = a.L, hl = a.head_len, NP = s.n_pairs;
+  __shared__ uint32_t present[32];  // one bit per bin (NP <= 990)
+  const bool sparse = NP > nw;      // block-uniform
+  for (int q = blockIdx.x; q < a.n_order; q += gridDim.x) {
+    const int bi = a.order[q];
+    const unsigned long long s0 = s.site_off[bi], s1 = s.site_off[bi + 1];
+    if (s0 == s1) continue;
+    const int st0 = a.status[bi];
+    const double pg = a.gprob[bi];
+    const bool resolved = (st0 == EST_OK || st0 == EST_OK_PRUNED) && pg > 0.0 && !isinf(pg);
+    if (!resolved || pg < SITE_PG_MIN) {  // rows of zeros: unresolved (1), or P(genotype) subnormal (2)
+      for (unsigned long long i = s0 * NP + threadIdx.x; i < s1 * NP; i += blockDim.x) s.post[i] = 0.0;
+      for (unsigned long long i = s0 + threadIdx.x; i < s1; i += blockDim.x) s.site_status[i] = resolved ? 2 : 1;
+      continue;
+    }
+    const unsigned long long *roff = a.rec_off + (size_t)bi * (L + 1);
+    const unsigned long long *xo = a.x_off + (size_t)bi * (L + 1);
+    // On long panels P(genotype) is tiny and a product fwd * bwd of two normal
+    // numbers would be subnormal or 0: both factors and the divisor are scaled
+    // by powers of two that cancel (fwd * bwd <= P(genotype), so nothing
+    // overflows).  Exact, so wherever the plain formula stays in the normal
+    // range this gives its bits.
+    const int sc = -ilogb(pg), sa = sc / 2, sb = sc - sa;
+    const double pgs = ldexp(pg, sc);
+    for (unsigned long long site = s0; site < s1; ++site) {
+      const int k = s.site_locus[site];
+      const bool head = k < hl - 1;  // alleles from the head patterns (head_len > 1 only)
+      const int j = head ? hl : k + 1;
+      const RecView R(a.rec + roff[j], j == hl);
+      const double *fw = (const double *)(a.x + xo[j]), *bw = fw + R.F;
+      const uint32_t *plo = R.cb + R.F + 1, *phi = plo + R.F;  // head record: the states' two head patterns
+      auto bin_of = [&](int t) -> uint32_t {
+        if (head) return xpair_index(a.head_al[(size_t)plo[t] * hl + k], a.head_al[(size_t)phi[t] * hl + k]);
+        const uint32_t h = R.hdr[t];
+        return xpair_index(h & 0xFFu, (h >> 8) & 0xFFu);
+      };
+      double *out = s.post + site * NP;
+      if (sparse) {
+        if (threadIdx.x < 32) present[threadIdx.x] = 0u;
+        __syncthreads();
+        for (int t = threadIdx.x; t < R.F; t += blockDim.x) {
+          const uint32_t b = bin_of(t);
+          if (b < (uint32_t)NP) atomicOr(&present[b >> 5], 1u << (b & 31u));
+        }
+        __syncthreads();
+      }
+      for (int b = wave; b < NP; b += nw) {  // wave-uniform
+        if (sparse && !((present[b >> 5] >> (b & 31)) & 1u)) {
+          if (lane == 0) out[b] = 0.0;
+          continue;
+        }
+        double part[1] = {0.0};
+        for (int t = lane; t < R.F; t += WAVE)
+          if (bin_of(t) == (uint32_t)b) part[0] += ldexp(fw[t], sa) * ldexp(bw[t], sb);
+        const double v = group_sum_fixed<WAVE>(part) / pgs;
+        if (lane == 0) out[b] = v;
+      }
+      if (threadIdx.x == 0) s.site_status[site] = 0;
+      if (sparse) __syncthreads();  // the bitmap is cleared for the next site
+    }
+  }
+}
+
+hipError_t launch_exact_site_posteriors(const ExactArgs &a, const SiteArgs &s, int grid, hipStream_t st, int block) {
+  if (a.n_order <= 0) return hipSuccess;
+  if (block < WAVE || block > 1024 || block % WAVE || grid < 1 || s.n_pairs != a.width * (a.width + 1) / 2 || !s.site_off ||
+      !s.post || !s.site_status)
+    return hipErrorInvalidValue;
+  hipLaunchKernelGGL(exact_site_posteriors, dim3(grid), dim3(block), 0, st, a, s);
+  return hipGetLastError();
+}
+
 }  // namespace hmc

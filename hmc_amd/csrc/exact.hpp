@@ -90,4 +90,18 @@ __host__ __device__ inline size_t exact_walk_lds_bytes(int max_depth, int fmax, 
 }
 constexpr size_t EXACT_WALK_LDS_MAX = 160 * 1024;  // gfx950 LDS per workgroup
 
+// Genotype posteriors at missing loci (exact_site_posteriors): the sites of
+// the shard's individuals as a CSR over batch indices, loci ascending; one
+// output row of n_pairs bins per site (bin of {x, y} = xpair_index(x, y)).
+struct SiteArgs {
+  const unsigned long long *site_off = nullptr;  // [batch + 1]
+  const int32_t *site_locus = nullptr;           // [sites]
+  double *post = nullptr;                        // [sites][n_pairs]
+  int32_t *site_status = nullptr;                // [sites] 0 ok; rows of zeros: 1 individual unresolved, 2 P(genotype) subnormal
+  int n_pairs = 0;                               // width (width + 1) / 2
+};
+constexpr double SITE_PG_MIN = 2.2250738585072014e-308;  // DBL_MIN: below it the likelihoods have lost their bits
+// after exact_fb over the same group; any block size that is a multiple of 64 gives the same bits
+hipError_t launch_exact_site_posteriors(const ExactArgs &a, const SiteArgs &s, int grid, hipStream_t st, int block = 256);
+
 }  // namespace hmc

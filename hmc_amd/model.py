@@ -475,6 +475,43 @@ class HaploModel:
         self._check(lib().hmc_get_resolutions(self._h, _p(out, C.c_int32)))
         return out
 
+    def genotype_posterior_shape(self) -> tuple[int, int]:
+        """(sites of this rank's shard, pairs per site) of genotype_posteriors,
+        counted from the panel without device work."""
+        ns, npairs = C.c_int64(), C.c_int()
+        self._check(lib().hmc_genotype_posteriors(self._h, C.byref(ns), C.byref(npairs), None, None, None, None))
+        return ns.value, npairs.value
+
+    def genotype_posteriors(self) -> dict:
+        """Posterior of the unordered genotype at every (individual, locus) of
+        this rank's shard where an input allele is missing, under the model of
+        the last resolve_all (hmc_genotype_posteriors): indiv[n], locus[n],
+        status[n] (0 ok; rows of zeros: 1 individual unresolved, 2 its
+        P(genotype) subnormal), post[n][NP], and
+        pairs[NP][2] = the allele indices (lo, hi) of each bin, which index
+        the locus's row of allele_table()."""
+        ns, NP = self.genotype_posterior_shape()
+        out = dict(indiv=np.zeros(ns, np.int32), locus=np.zeros(ns, np.int32), status=np.zeros(ns, np.int32),
+                   post=np.zeros((ns, NP), np.float64),
+                   pairs=np.array([(lo, hi) for hi in range(self.amax) for lo in range(hi + 1)], np.int32).reshape(NP, 2))
+        n2 = C.c_int64()
+        self._check(lib().hmc_genotype_posteriors(self._h, C.byref(n2), None, _p(out["indiv"], C.c_int32),
+                                                  _p(out["locus"], C.c_int32), _p(out["status"], C.c_int32),
+                                                  _p(out["post"], C.c_double)))
+        assert n2.value == ns
+        return out
+
+    def posterior_stats(self) -> dict:
+        """Device ms and counts of the last genotype_posteriors (hmc_last_posterior_stats)."""
+        s, f, k = C.c_double(), C.c_double(), C.c_double()
+        g, p = C.c_int(), C.c_int()
+        self._check(lib().hmc_last_posterior_stats(self._h, C.byref(s), C.byref(f), C.byref(k), C.byref(g), C.byref(p)))
+        return dict(structure_ms=s.value, fb_ms=f.value, sites_ms=k.value, groups=g.value, n_pruned=p.value)
+
+    def write_posteriors(self, path: str):
+        """genotype_posteriors as text, one line per site and non-zero pair (hmc_write_posteriors)."""
+        self._check(lib().hmc_write_posteriors(self._h, path.encode()))
+
     def timings(self) -> dict:
         f, t, m = C.c_double(), C.c_double(), C.c_double()
         self._check(lib().hmc_last_timings(self._h, C.byref(f), C.byref(t), C.byref(m)))

@@ -241,6 +241,42 @@ int hmc_clear_samples(hmc_ctx *ctx);
 /* Selected pair per individual of the last E-step ([n][2][L] symbols;
  * unresolved individuals keep the input genotype, HaploBuilder.cpp:117-124). */
 int hmc_get_resolutions(hmc_ctx *ctx, int32_t *out);
+/* Posterior of the unordered genotype at every (individual, locus) of this
+ * rank's shard where an input allele is missing, under the current model:
+ * P({x, y} at the locus | genotype) = the sum of forward x backward likelihood
+ * over the lattice states that carry {x, y}, over P(genotype) — exact, with no
+ * k-best cut and no sampling (hmc_get_resolutions gives the alleles of the
+ * single most probable pair only).  Needs a preceding hmc_resolve_all (any
+ * E-step mode); runs its own forward-backward pass and changes no later
+ * result.  With indiv, locus, status and post all NULL the call only counts:
+ * *n_sites from the panel, *n_pairs = A (A + 1) / 2 for A = max_alleles
+ * (hmc_panel_info), and no device work.  Otherwise (any of the four may be
+ * NULL) sites come individual-major with loci ascending: indiv[n_sites]
+ * (panel index), locus[n_sites], status[n_sites], post[n_sites][n_pairs].
+ * status: 0 ok; 1 the individual is unresolved; 2 the individual's
+ * P(genotype) (hmc_get_estep's total) is subnormal, below DBL_MIN — panels of
+ * thousands of loci: the likelihoods are raw doubles and have lost their bits
+ * there, a row could miss 1 by any amount.  Rows of status 1 and 2 are zeros.
+ * Bin hi (hi + 1) / 2 + lo holds the pair of allele indices lo <= hi, which
+ * index the locus's allele table (hmc_allele_table: sym[locus][lo],
+ * sym[locus][hi]); bins no state carries are 0.  A row of status 0 sums to 1
+ * up to rounding.  A site at a
+ * locus below head_len (an individual with a missing allele at a head locus)
+ * comes from the reference's head pairing (initHeadList, HaploBuilder.cpp:
+ * 153-224), which is not a phasing model: only its normalisation holds there.
+ * HMC_EARG when no E-step has run or the model has changed since the last one
+ * (an M-step, hmc_set_patterns): P(genotype) of that E-step is the divisor.
+ * The bits do not depend on launch shapes, store budgets or sharding.
+ * HMC_EUNSUPPORTED as for the exact M-step (more than 44 alleles at a locus,
+ * too many contributions at a locus, an injected table with head_len > 1).
+ * Replaces no reference interface. */
+int hmc_genotype_posteriors(hmc_ctx *ctx, int64_t *n_sites, int *n_pairs, int32_t *indiv, int32_t *locus, int32_t *status,
+                            double *post);
+/* Last hmc_genotype_posteriors: device ms of its structure passes, of the
+ * forward-backward kernel and of the site kernel; groups the individuals ran
+ * in; individuals on pruned records (underflowing forward likelihoods). */
+int hmc_last_posterior_stats(const hmc_ctx *ctx, double *structure_ms, double *fb_ms, double *sites_ms, int *groups,
+                             int *n_pruned);
 
 /* ---- whole EM: HaploModel::run (HaploModel.cpp:117-155) ------------------ */
 typedef struct hmc_iter_log {
@@ -323,6 +359,14 @@ int hmc_write_file(hmc_ctx *ctx, const char *format, const char *path, const cha
  * The reference divides by genotype_num() of a GenoData that no longer exists
  * when it writes, so the N used here is the panel's: unpinned. */
 int hmc_write_patterns(hmc_ctx *ctx, const char *path);
+/* hmc_genotype_posteriors as text (hmc_resolve --output-posteriors): the
+ * header "Id\tMarker\tAlleleLo\tAlleleHi\tPosterior", then one line per site
+ * and pair of non-zero probability, in the call's site order and then bin
+ * order: individual id, marker name, the two allele symbols as the genotype
+ * files spell them, the posterior as %.17g (reads back to the same double).
+ * Needs a preceding hmc_resolve_all or hmc_run; the numbers belong to the
+ * model of that last E-step.  Replaces no reference interface. */
+int hmc_write_posteriors(hmc_ctx *ctx, const char *path);
 
 /* ---- tuning -------------------------------------------------------------- */
 /* frontier_cap: initial states per locus and individual (doubles on

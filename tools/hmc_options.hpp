@@ -14,8 +14,30 @@ struct Options {
   std::vector<std::string> files;
   std::string model = "MV", format = "PHASE";
   int mc_order = 1, num_patterns = -1;
-  bool exact = false, output_patterns = false;
+  bool exact = false, output_patterns = false, output_posteriors = false;
 };
+
+// --output-posteriors (no reference counterpart): <first file>.posteriors, the
+// posterior of every unordered genotype at the loci where an input allele is
+// missing.  The numbers belong to the model of the run's last E-step — the
+// final model, since the EM always ends on an E-step — which is not the model
+// of the written resolutions when that last E-step's likelihood dropped.
+constexpr const char *USAGE =
+    "Usage: hmc_resolve [option ...] datafiles\n"
+    "  -f, --input-format F  PHASE (default), HPM, HPM2, BENCH2 or BENCH3\n"
+    "  -a, --min-freq-abs X  minimum pattern frequency in haplotypes (default 1.5)\n"
+    "  -r, --min-freq-rel X  minimum pattern frequency as a fraction (replaces -a)\n"
+    "  -n, --num-patterns N  mine by pattern count instead of frequency\n"
+    "  -m, --model M         MV (default), MC or MA;  -o, --mc-order K (default 1)\n"
+    "  -i, --max-iteration N EM iterations (default 1)\n"
+    "  --sample-size S       candidates kept per individual (default 10)\n"
+    "  --min-pattern-len N   (default 1)   --max-pattern-len N   (default 30)\n"
+    "  --exact-estimate      M-steps by expected counts instead of sampling\n"
+    "  --output-patterns X   also write <datafile>.patterns\n"
+    "  --device D            GPU index (default 0)\n"
+    "  -d, --debug LEVEL     accepted and ignored\n"
+    "  --output-posteriors   write <datafile>.posteriors: genotype posteriors at missing loci under the\n"
+    "                        final model (the model of the last E-step of the run)";
 
 // 0 on success; otherwise `err` says what is wrong (a missing value, an
 // unknown option, no data file).
@@ -42,6 +64,7 @@ inline int parse_options(int argc, const char *const *argv, Options &o, std::str
     else if (a == "-f" || a == "--input-format") { if (!next()) return 1; o.format = v; }  // HMC.cpp:29
     else if (a == "--exact-estimate") o.exact = true;                                      // HMC.cpp:42
     else if (a == "--output-patterns") { if (!next()) return 1; o.output_patterns = true; }  // HMC.cpp:30, 229-232
+    else if (a == "--output-posteriors") o.output_posteriors = true;
     else if (a == "-m" || a == "--model") { if (!next()) return 1; o.model = v; }          // HMC.cpp:35
     else if (a == "-o" || a == "--mc-order") { if (!next()) return 1; o.mc_order = atoi(v); }      // HMC.cpp:41
     else if (a == "-n" || a == "--num-patterns") { if (!next()) return 1; o.num_patterns = atoi(v); }  // HMC.cpp:38
@@ -49,7 +72,7 @@ inline int parse_options(int argc, const char *const *argv, Options &o, std::str
     else o.files.push_back(a);
   }
   if (o.files.empty()) {
-    err = "Usage: hmc_resolve [option ...] datafiles";
+    err = USAGE;
     return 1;
   }
   return 0;
