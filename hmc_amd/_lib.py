@@ -133,6 +133,7 @@ _SIGS = [
     ("hmc_test_nth_element_masks", None, [_P(_d), _P(C.c_uint32), _i, _i]),
     ("hmc_test_coop_nth_element", _i, [_i, _P(_d), _P(C.c_uint32), _P(C.c_int32), _P(C.c_int32), _P(C.c_int32),
                                        _i, _i, _i]),
+    ("hmc_test_coop_select", _i, [_i, _i, _i, _P(_d), _P(C.c_uint32), _P(C.c_int32), _P(C.c_int32), _P(_d), _i]),
 ]
 
 EXPORTED = [s[0] for s in _SIGS]

@@ -1053,6 +1053,40 @@ int hmc_test_coop_nth_element(int device, double *lik, uint32_t *tag, const int3
   return HMC_OK;
 }
 
+int hmc_test_coop_select(int device, int mode, int width, double *lik, uint32_t *tag, const int32_t *n,
+                         const int32_t *nth, double *tie, int count) {
+  // shapes are checked before the device is touched: the hook, not the kernel, refuses them
+  if (mode < HMC_SELECT_PAIR || mode > HMC_SELECT_RANK || count < 0 || !lik || !tag || !n) return HMC_EARG;
+  const bool wide = mode == HMC_SELECT_WIDE, rank = mode == HMC_SELECT_RANK;
+  if (wide ? width != 64 : (width < 1 || width > 16)) return HMC_EARG;
+  if ((mode == HMC_SELECT_PAIR10 && width != 10) || (rank ? !tie : !nth)) return HMC_EARG;
+  const int stride = wide ? 128 : 2 * width;
+  for (int j = 0; j < count; ++j)
+    if (n[j] < 0 || n[j] > stride || (!rank && (nth[j] < 0 || nth[j] > n[j]))) return HMC_EARG;
+  if (hipSetDevice(device) != hipSuccess) return HMC_EHIP;
+  if (count == 0) return HMC_OK;
+  const size_t total = (size_t)count * stride;
+  hmc::DevBuf<double> dl, dtie;
+  hmc::DevBuf<uint32_t> dt;
+  hmc::DevBuf<int32_t> dn, dnth;
+  hipError_t e;
+  if ((e = dl.ensure(total)) || (e = dt.ensure(total)) || (e = dn.ensure(count)) || (e = dnth.ensure(count)) ||
+      (e = dtie.ensure(count)))
+    return HMC_EHIP;
+  if ((e = hipMemcpy(dl.p, lik, total * 8, hipMemcpyHostToDevice)) ||
+      (e = hipMemcpy(dt.p, tag, total * 4, hipMemcpyHostToDevice)) ||
+      (e = hipMemcpy(dn.p, n, (size_t)count * 4, hipMemcpyHostToDevice)) ||
+      (e = hipMemcpy(dnth.p, rank ? n : nth, (size_t)count * 4, hipMemcpyHostToDevice)) ||
+      (e = hipMemset(dtie.p, 0, (size_t)count * 8)))
+    return HMC_EHIP;
+  if ((e = hmc::launch_test_select(mode, width, dl.p, dt.p, dn.p, dnth.p, dtie.p, count, nullptr))) return HMC_EHIP;
+  if ((e = hipMemcpy(lik, dl.p, total * 8, hipMemcpyDeviceToHost)) ||
+      (e = hipMemcpy(tag, dt.p, total * 4, hipMemcpyDeviceToHost)) ||
+      (rank && (e = hipMemcpy(tie, dtie.p, (size_t)count * 8, hipMemcpyDeviceToHost))))
+    return HMC_EHIP;
+  return HMC_OK;
+}
+
 void hmc_test_nth_element_masks(double *lik, uint32_t *tag, int n, int nth) {
   hmc::LinkList v{lik, tag, 1};
   hmc::nth_element_greater_masks(v, n, nth, n);

@@ -2385,4 +2385,82 @@ hipError_t launch_estep_values(const ValueArgs &a, int grid, int nw, bool fast, 
   return hipGetLastError();
 }
 
+// Test kernel: the selection layouts of estep_values outside an E-step, one
+// wavefront per block, with the scratch estep_values gives one wave (k2_plan)
+// and its segmentation.  List j is lik/tag[j * stride, (j + 1) * stride), its
+// first n[j] slots the list; the whole stride is loaded and stored back, so
+// the caller sees that nothing behind a list was touched.
+// MODE 0: two links per lane (seg2_nth_slots, make_seg(W), stride 2W; WC > 0:
+// W fixed at compile time, as estep_values<.., PAIR, SC> has it); 1: one list
+// of up to 128 links per wave (the sw > 32 path of seg_nth_slots, stride
+// 128); 2: value-only lists (seg_rank_select(n, W, make_seg(2W)), stride 2W),
+// tie[j] = the largest return of the segment's lanes.
+template <int MODE, int WC>
+__global__ __launch_bounds__(64) void test_select_layout(double *lik, uint32_t *tag, const int *n, const int *nth,
+                                                         double *tie, int count, int w_rt) {
+  extern __shared__ __align__(16) unsigned char smem[];
+  constexpr bool PAIR = MODE == 0, WIDE = MODE == 1;
+  const int W = WC > 0 ? WC : w_rt;
+  const K2Plan plan = k2_plan(WIDE ? WAVE : W, 0, 1, PAIR);
+  const int sws = k2_slots(WIDE ? WAVE : W, PAIR);
+  const SegScratch ss{(int *)(smem + plan.o_lpos), (int *)(smem + plan.o_rpos), (int *)(smem + plan.o_junk),
+                      (double *)(smem + plan.o_slik), (uint32_t *)(smem + plan.o_smeta)};
+  const Seg sg = make_seg(WIDE ? WAVE : (PAIR ? W : 2 * W));
+  const int G = WIDE ? 1 : (PAIR ? WAVE / W : WAVE / (2 * W));
+  const int stride = WIDE ? 2 * WAVE : 2 * W;
+  const int step = WIDE ? WAVE : (PAIR ? W : 2 * W);  // this lane carries positions k and k + step (< stride)
+  const int sb = PAIR ? sg.g * 2 * W : sg.base;       // the segment's first slot (PAIR: dead lanes, a dead segment)
+  const int lane = (int)(threadIdx.x & 63);
+  for (int q = lane; q < sws; q += WAVE) {
+    ss.slik[q] = 0.0;
+    ss.smeta[q] = 0u;
+  }
+  wave_lds_sync();
+  const int j = blockIdx.x * G + sg.g;
+  const bool mine = sg.g < G && j < count;
+  const int nj = mine ? n[j] : 0, nthj = mine ? nth[j] : 0;
+  if (mine)
+    for (int p = sg.k; p < stride; p += step) {
+      ss.slik[sb + p] = lik[(size_t)j * stride + p];
+      ss.smeta[sb + p] = tag[(size_t)j * stride + p];
+    }
+  wave_lds_sync();
+  if constexpr (MODE == 2) {
+    const double tv = seg_rank_select(nj, W, sg, ss);
+    double best = 0.0;
+    for (int q = 0; q < 2 * W; ++q) {
+      const double t = gat_f64(tv, sg.base + q);
+      best = t > best ? t : best;
+    }
+    if (mine && sg.k == 0) tie[j] = best;
+  } else if constexpr (PAIR) {
+    seg2_nth_slots(nj, nthj, sg, ss);
+  } else {
+    seg_nth_slots(nj, nthj, sg, ss);
+  }
+  wave_lds_sync();
+  if (mine)
+    for (int p = sg.k; p < stride; p += step) {
+      lik[(size_t)j * stride + p] = ss.slik[sb + p];
+      tag[(size_t)j * stride + p] = ss.smeta[sb + p];
+    }
+}
+
+hipError_t launch_test_select(int mode, int width, double *lik, uint32_t *tag, const int *n, const int *nth,
+                              double *tie, int count, hipStream_t st) {
+  if (count <= 0) return hipSuccess;
+  const bool pair = mode == 0 || mode == 1, wide = mode == 2;
+  if (mode < 0 || mode > 3 || (wide ? width != WAVE : (width < 1 || width > 16)) || (mode == 1 && width != 10) ||
+      (mode == 3 && !tie))
+    return hipErrorInvalidValue;
+  const int G = wide ? 1 : (pair ? WAVE / width : WAVE / (2 * width));
+  const size_t lds = (size_t)k2_plan(width, 0, 1, pair).bytes;
+  const dim3 grid((count + G - 1) / G), block(WAVE);
+  if (mode == 0) hipLaunchKernelGGL((test_select_layout<0, 0>), grid, block, lds, st, lik, tag, n, nth, tie, count, width);
+  else if (mode == 1) hipLaunchKernelGGL((test_select_layout<0, 10>), grid, block, lds, st, lik, tag, n, nth, tie, count, width);
+  else if (mode == 2) hipLaunchKernelGGL((test_select_layout<1, 0>), grid, block, lds, st, lik, tag, n, nth, tie, count, width);
+  else hipLaunchKernelGGL((test_select_layout<2, 0>), grid, block, lds, st, lik, tag, n, nth, tie, count, width);
+  return hipGetLastError();
+}
+
 }  // namespace hmc

@@ -349,6 +349,9 @@ hipError_t launch_estep_trace_gc(const TraceGcArgs &a, int grid, hipStream_t st)
 size_t estep_scratch_bytes(int fcap, int hcap, int S, int nw);
 size_t estep_lds_bytes(int S, int fc, int hc, int nw, int amax);
 hipError_t launch_test_coop_nth(double *lik, uint32_t *tag, const int *off, const int *n, const int *nth, int count, int sw, hipStream_t st);
+// mode 0: pair layout, width = W; 1: pair layout, W = 10 at compile time; 2: wide (width 64); 3: rank select, width = S
+hipError_t launch_test_select(int mode, int width, double *lik, uint32_t *tag, const int *n, const int *nth, double *tie,
+                              int count, hipStream_t st);
 hipError_t launch_estep(const EstepArgs &a, int grid, int nw, hipStream_t st);
 size_t estep_s1_scratch_bytes(int fcap, int hcap, int ccap, int nw, bool prune = false);
 size_t estep_s1_lds_bytes(int fc, int hc, int cc, int amax, int nw);

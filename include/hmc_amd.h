@@ -525,6 +525,23 @@ void hmc_test_nth_element_masks(double *lik, uint32_t *tag, int n, int nth);
  * nth_element(.., nth[b], greater) in place on `device`. */
 int hmc_test_coop_nth_element(int device, double *lik, uint32_t *tag, const int32_t *off, const int32_t *n,
                               const int32_t *nth, int count, int total, int seg_width);
+/* GPU check of the other selection layouts of the E-step's value pass, each
+ * with the scratch and segmentation the pass gives it.  List b occupies
+ * lik/tag[b*stride .. (b+1)*stride), its first n[b] entries the list; the rest
+ * must come back unchanged.
+ *   HMC_SELECT_PAIR    two links per lane, `width` = W lanes per list (1..16),
+ *                      stride 2W, n[b] <= 2W: nth_element(.., nth[b], greater)
+ *   HMC_SELECT_PAIR10  the same with W = 10 fixed at compile time (width 10)
+ *   HMC_SELECT_WIDE    one list of n[b] <= 128 per wavefront (width 64),
+ *                      stride 128: nth_element(.., nth[b], greater)
+ *   HMC_SELECT_RANK    value-only lists, `width` = S (1..16), stride 2S,
+ *                      n[b] <= 2S: the S largest to [0, S) in rank order when
+ *                      n[b] > S; tie[b] = the non-zero value tied across the
+ *                      S-cut, else 0 (values >= 0, no NaN; nth is not read)
+ * Shapes the value pass does not instantiate are refused (HMC_EARG). */
+enum { HMC_SELECT_PAIR = 0, HMC_SELECT_PAIR10 = 1, HMC_SELECT_WIDE = 2, HMC_SELECT_RANK = 3 };
+int hmc_test_coop_select(int device, int mode, int width, double *lik, uint32_t *tag, const int32_t *n,
+                         const int32_t *nth, double *tie, int count);
 /* Library version string. */
 const char *hmc_version(void);
 /* Version, target, flags and build time of this libhmc_amd.so (bench.py
