@@ -83,6 +83,9 @@ _SIGS = [
     ("hmc_get_resolutions", _i, [_vp, _P(C.c_int32)]),
     ("hmc_genotype_posteriors", _i, [_vp, _P(C.c_int64), _P(_i), _P(C.c_int32), _P(C.c_int32), _P(C.c_int32), _P(_d)]),
     ("hmc_last_posterior_stats", _i, [_vp, _P(_d), _P(_d), _P(_d), _P(_i), _P(_i)]),
+    ("hmc_switch_posteriors", _i, [_vp, _P(C.c_int64), _P(C.c_int32), _P(C.c_int32), _P(C.c_int32), _P(C.c_int32), _P(_d)]),
+    ("hmc_last_switch_stats", _i, [_vp, _P(_d), _P(_d), _P(_d), _P(_i), _P(_i), _P(_i)]),
+    ("hmc_set_switch_tier", _i, [_vp, _i]),
     ("hmc_clear_samples", _i, [_vp]),
     ("hmc_run", _i, [_vp, _i, _P(IterLog), _i, _P(_i), _P(_d), _P(_u64), _P(_i)]),
     ("hmc_em_iteration", _i, [_vp, _i, _i, _i, _P(_d), _P(IterLog), _P(_i)]),
@@ -102,6 +105,7 @@ _SIGS = [
     ("hmc_write_patterns", _i, [_vp, _cp]),
     ("hmc_write_phase", _i, [_vp, _cp]),
     ("hmc_write_posteriors", _i, [_vp, _cp]),
+    ("hmc_write_switch_posteriors", _i, [_vp, _cp]),
     ("hmc_set_tuning", _i, [_vp, _i, _u64, _i]),
     ("hmc_set_estep_shape", _i, [_vp, _i, _i]),
     ("hmc_set_pass_shapes", _i, [_vp, _i, _i, _i, _i]),

@@ -904,6 +904,41 @@ int hmc_last_posterior_stats(const hmc_ctx *h, double *structure_ms, double *fb_
   return HMC_OK;
 }
 
+int hmc_switch_posteriors(hmc_ctx *h, int64_t *n_sites, int32_t *indiv, int32_t *locus_a, int32_t *locus_b, int32_t *status,
+                          double *post) {
+  if (!h) return HMC_EARG;
+  Ctx &c = h->c;
+  if (!c.have_panel) return c.fail(HMC_EARG, "no panel loaded");
+  if (!indiv && !locus_a && !locus_b && !status && !post) {  // count only: no device work
+    Ctx::SwitchList sl;
+    c.switch_list(sl);
+    if (n_sites) *n_sites = (int64_t)sl.locus_a.size();
+    return HMC_OK;
+  }
+  const int rc = c.switch_posteriors(indiv, locus_a, locus_b, status, post);
+  if (rc) return rc;
+  if (n_sites) *n_sites = (int64_t)c.n_switch_last;
+  return HMC_OK;
+}
+
+int hmc_last_switch_stats(const hmc_ctx *h, double *structure_ms, double *fb_ms, double *sweep_ms, int *groups, int *n_pruned,
+                          int *n_spilled) {
+  if (!h) return HMC_EARG;
+  if (structure_ms) *structure_ms = h->c.sw_ms_struct;
+  if (fb_ms) *fb_ms = h->c.sw_ms_fb;
+  if (sweep_ms) *sweep_ms = h->c.sw_ms_sweep;
+  if (groups) *groups = h->c.sw_groups;
+  if (n_pruned) *n_pruned = h->c.sw_pruned;
+  if (n_spilled) *n_spilled = h->c.sw_spilled;
+  return HMC_OK;
+}
+
+int hmc_set_switch_tier(hmc_ctx *h, int states) {
+  if (!h || states < 0 || states > hmc::SWITCH_TIER_MAX) return HMC_EARG;
+  h->c.sw_tier = states;
+  return HMC_OK;
+}
+
 int hmc_run(hmc_ctx *h, int max_iteration, hmc_iter_log *log, int log_cap, int *iterations, double *t_m0_s,
             uint64_t *r_m0, int *n_patterns0) {
   if (!h) return HMC_EARG;
@@ -1008,6 +1043,39 @@ int hmc_write_posteriors(hmc_ctx *h, const char *path) {
       }
   }
   // a write that failed anywhere (a full disk) leaves the stream's error flag set, or fails the close
+  const bool bad = ferror(fp) != 0;
+  if (fclose(fp) != 0 || bad) return c.fail(HMC_EIO, "Can not write file %s!", path);
+  return HMC_OK;
+}
+
+int hmc_write_switch_posteriors(hmc_ctx *h, const char *path) {
+  if (!h || !path || !h->c.have_panel) return HMC_EARG;
+  Ctx &c = h->c;
+  Ctx::SwitchList sl;
+  c.switch_list(sl);
+  const size_t ns = sl.locus_a.size();
+  std::vector<int32_t> indiv(ns), status(ns);
+  std::vector<double> post(ns * 2);
+  int rc;
+  if ((rc = c.switch_posteriors(indiv.data(), nullptr, nullptr, status.data(), post.data(), &sl))) return rc;
+  FILE *fp = fopen(path, "w");
+  if (!fp) return c.fail(HMC_EIO, "Can not open file %s!", path);
+  const hmc::FileData d = writer_meta(c);
+  fprintf(fp, "Id\tMarkerA\tMarkerB\tAlleleA\tAlleleB\tCis\tTrans\n");
+  auto put_lower = [&](int i, int k) {  // the lower-index allele of the two, as the genotype files spell alleles
+    const uint8_t *g0 = c.pan.idx.data() + ((size_t)i * 2) * c.pan.L, *g1 = g0 + c.pan.L;
+    const int32_t a = c.pan.symbol(k, std::min(g0[k], g1[k]));
+    if (c.pan.types[k] == 'S') fprintf(fp, "\t%c", (char)a);
+    else fprintf(fp, "\t%d", a);
+  };
+  for (size_t q = 0; q < ns; ++q) {
+    if (status[q] != 0) continue;
+    const int ka = sl.locus_a[q], kb = sl.locus_b[q];
+    fprintf(fp, "%s\t%s\t%s", d.ids[indiv[q]].c_str(), d.names[ka].c_str(), d.names[kb].c_str());
+    put_lower(indiv[q], ka);
+    put_lower(indiv[q], kb);
+    fprintf(fp, "\t%.17g\t%.17g\n", post[2 * q], post[2 * q + 1]);
+  }
   const bool bad = ferror(fp) != 0;
   if (fclose(fp) != 0 || bad) return c.fail(HMC_EIO, "Can not write file %s!", path);
   return HMC_OK;

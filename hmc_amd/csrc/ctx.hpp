@@ -807,7 +807,31 @@ struct Ctx {
   int site_posteriors(int32_t *indiv, int32_t *locus, int32_t *status, double *post, const SiteList *pre = nullptr);
   void site_list(SiteList &sl) const;
   int site_group(const ExactArgs &x, int k, int dev_cu);
-  bool xp_mode = false;
+  // what the exact group runs after exact_fb in place of the trie walk
+  enum XpMode { XP_OFF = 0, XP_GENOTYPE = 1, XP_SWITCH = 2 };
+  XpMode xp_mode = XP_OFF;
+  // The part the two posterior calls share: every individual of the shard
+  // through estep_split(order, true) with xp_mode = mode, and whatever that
+  // pass shares with the E-step saved before and put back after.
+  int xp_pass(XpMode mode, const char *what);
+  // Switch posteriors (hmc_switch_posteriors): sites are an individual's pairs
+  // of consecutive heterozygous loci, individual-major, locus_a ascending;
+  // exact_switch_posteriors per group (XP_SWITCH).
+  struct SwitchList {
+    std::vector<unsigned long long> off;  // [n + 1] over the shard's individuals
+    std::vector<int32_t> locus_a, locus_b;
+  };
+  int switch_posteriors(int32_t *indiv, int32_t *locus_a, int32_t *locus_b, int32_t *status, double *post,
+                        const SwitchList *pre = nullptr);
+  void switch_list(SwitchList &sl) const;
+  int switch_group(const ExactArgs &x, const int32_t *ids, const std::vector<int32_t> &fm, int k, int dev_cu);
+  DevBuf<int32_t> d_sw_a, d_sw_b;
+  DevBuf<double> d_sw_scratch;
+  int sw_tier = 0;  // hmc_set_switch_tier (0: SWITCH_TIER_DEFAULT)
+  // of the last call, as xp_* below; sw_spilled: individuals whose largest record exceeded the tier
+  double sw_ms_struct = 0, sw_ms_fb = 0, sw_ms_sweep = 0;
+  int sw_groups = 0, sw_pruned = 0, sw_spilled = 0;
+  size_t n_switch_last = 0;
   DevBuf<unsigned long long> d_site_off;
   DevBuf<int32_t> d_site_locus, d_site_status;
   DevBuf<double> d_site_post;

@@ -249,8 +249,108 @@ int Ctx::exact_group(const int32_t *ids, int k, const std::function<int(std::vec
   xc_fmax = fmax;
   xc_k = k;
   ++xc_groups;
-  if (xp_mode) return site_group(x, k, dev_cu);  // genotype posteriors: no trie, no walk
+  if (xp_mode == XP_GENOTYPE) return site_group(x, k, dev_cu);  // genotype posteriors: no trie, no walk
+  if (xp_mode == XP_SWITCH) return switch_group(x, ids, fm, k, dev_cu);
   return exact_walk_group(x, k, dev_cu);
+}
+
+int Ctx::switch_group(const ExactArgs &x, const int32_t *ids, const std::vector<int32_t> &fm, int k, int dev_cu) {
+  SwitchArgs s;
+  s.site_off = d_site_off.p;
+  s.locus_a = d_sw_a.p;
+  s.locus_b = d_sw_b.p;
+  s.post = d_site_post.p;
+  s.site_status = d_site_status.p;
+  s.tier = sw_tier > 0 ? sw_tier : SWITCH_TIER_DEFAULT;
+  int grid = std::max(1, std::min(k, dev_cu * 8));
+  hipError_t e;
+  int spilled = 0;
+  for (int q = 0; q < k; ++q) spilled += fm[ids[q]] > s.tier;
+  sw_spilled += spilled;
+  if (spilled) {  // frontiers past the tier: 32 B per state and block in HBM, at most 1 GiB (the grid does not change the bits)
+    grid = (int)std::max<size_t>(1, std::min<size_t>((size_t)grid, ((size_t)1 << 30) / ((size_t)32 * x.fmax)));
+    if ((e = d_sw_scratch.ensure((size_t)grid * 4 * x.fmax))) return hipfail(e, "exact_switch_posteriors");
+    s.scratch = d_sw_scratch.p;
+    s.scratch_states = x.fmax;
+  }
+  hipEventRecord(ev[0], st);
+  if ((e = launch_exact_switch_posteriors(x, s, grid, st))) return hipfail(e, "exact_switch_posteriors");
+  hipEventRecord(ev[1], st);
+  if ((e = sync_st())) return hipfail(e, "exact_switch_posteriors");
+  float ms = 0;
+  hipEventElapsedTime(&ms, ev[0], ev[1]);
+  xp_ms_sites += ms;
+  return HMC_OK;
+}
+
+void Ctx::switch_list(SwitchList &sl) const {
+  const int n = nloc(), L = pan.L;
+  sl.off.assign((size_t)n + 1, 0);
+  sl.locus_a.clear();
+  sl.locus_b.clear();
+  for (int i = 0; i < n; ++i) {
+    const uint8_t *g0 = pan.idx.data() + ((size_t)(i0 + i) * 2) * L, *g1 = g0 + L;
+    int last = -1;  // the heterozygous locus before k
+    for (int k = 0; k < L; ++k) {
+      if (g0[k] == MISSING || g1[k] == MISSING || g0[k] == g1[k]) continue;
+      if (last >= 0) {
+        sl.locus_a.push_back(last);
+        sl.locus_b.push_back(k);
+      }
+      last = k;
+    }
+    sl.off[i + 1] = sl.locus_a.size();
+  }
+}
+
+int Ctx::switch_posteriors(int32_t *indiv, int32_t *locus_a, int32_t *locus_b, int32_t *status, double *post,
+                           const SwitchList *pre) {
+  if (!have_estep) return fail(HMC_EARG, "switch posteriors need an E-step first (hmc_resolve_all)");
+  if (estep_gen != model_gen)
+    return fail(HMC_EARG, "switch posteriors: the model changed since the last E-step (hmc_resolve_all again)");
+  if (pan.amax > 44) return fail(HMC_EUNSUPPORTED, "switch posteriors with more than 44 alleles per locus");
+  const int n = nloc();
+  SwitchList own;
+  if (!pre) switch_list(own);
+  const SwitchList &sl = pre ? *pre : own;
+  const size_t ns = sl.locus_a.size();
+  n_switch_last = ns;
+  sw_ms_struct = sw_ms_fb = sw_ms_sweep = 0;
+  sw_groups = sw_pruned = sw_spilled = 0;
+  if (indiv)
+    for (int i = 0; i < n; ++i)
+      for (unsigned long long q = sl.off[i]; q < sl.off[i + 1]; ++q) indiv[q] = i0 + i;
+  if (locus_a && ns) std::copy(sl.locus_a.begin(), sl.locus_a.end(), locus_a);
+  if (locus_b && ns) std::copy(sl.locus_b.begin(), sl.locus_b.end(), locus_b);
+  if (ns == 0) return HMC_OK;
+  hipError_t er;
+  if ((er = d_site_off.ensure((size_t)n + 1)) || (er = d_sw_a.ensure(ns)) || (er = d_sw_b.ensure(ns)) ||
+      (er = d_site_status.ensure(ns)) || (er = d_site_post.ensure(ns * 2)) || (er = d_xstatus.ensure(n)) ||
+      (er = d_xre.ensure(n)) || (er = d_xfmax.ensure(n)) ||
+      (er = hipMemcpyAsync(d_site_off.p, sl.off.data(), ((size_t)n + 1) * 8, hipMemcpyHostToDevice, st)) ||
+      (er = hipMemcpyAsync(d_sw_a.p, sl.locus_a.data(), ns * 4, hipMemcpyHostToDevice, st)) ||
+      (er = hipMemcpyAsync(d_sw_b.p, sl.locus_b.data(), ns * 4, hipMemcpyHostToDevice, st)) ||
+      (er = hipMemsetAsync(d_site_post.p, 0, ns * 2 * 8, st)) || (er = hipMemsetAsync(d_site_status.p, 0, ns * 4, st)))
+    return hipfail(er, "switch posteriors");
+  // the pass counts in the genotype posteriors' fields: theirs are put back
+  const double g_struct = xp_ms_struct, g_fb = xp_ms_fb, g_sites = xp_ms_sites;
+  const int g_groups = xp_groups, g_pruned = xp_pruned;
+  const int rc = xp_pass(XP_SWITCH, "switch posteriors");
+  sw_ms_struct = xp_ms_struct;
+  sw_ms_fb = xp_ms_fb;
+  sw_ms_sweep = xp_ms_sites;
+  sw_groups = xp_groups;
+  sw_pruned = xp_pruned;
+  xp_ms_struct = g_struct;
+  xp_ms_fb = g_fb;
+  xp_ms_sites = g_sites;
+  xp_groups = g_groups;
+  xp_pruned = g_pruned;
+  if (rc) return rc;
+  if ((status && (er = hipMemcpyAsync(status, d_site_status.p, ns * 4, hipMemcpyDeviceToHost, st))) ||
+      (post && (er = hipMemcpyAsync(post, d_site_post.p, ns * 2 * 8, hipMemcpyDeviceToHost, st))) || (er = sync_st()))
+    return hipfail(er, "switch posteriors");
+  return HMC_OK;
 }
 
 int Ctx::site_group(const ExactArgs &x, int k, int dev_cu) {
@@ -285,6 +385,59 @@ void Ctx::site_list(SiteList &sl) const {
   }
 }
 
+int Ctx::xp_pass(XpMode mode, const char *what) {
+  hipError_t er;
+  // What the exact-mode structure pass shares with the E-step and a later call
+  // can see is put back afterwards: the last E-step's pass times and counts,
+  // its per-individual status (hmc_get_estep), the frontier statistic and the
+  // structure stamps, and the capacities a restart may have grown.  The stores
+  // (records, traces) are dead between an E-step and the next M- or E-step.
+  const double s1_0 = ms_s1, fb_0 = ms_fb;
+  const int passes_0 = n_struct_passes, pruned_0 = exact_pruned, fcap_0 = fcap, ccap_0 = ccap_mult;
+  const uint64_t rec_words_0 = rec_words;
+  const std::vector<int32_t> status_0 = h_status;
+  uint32_t maxst_0 = 0;
+  unsigned long long stamps_0[20] = {};
+  if ((er = hipMemcpyAsync(&maxst_0, d_maxst.p, 4, hipMemcpyDeviceToHost, st)) ||
+      (er = hipMemcpyAsync(stamps_0, d_stamps.p + 20, sizeof stamps_0, hipMemcpyDeviceToHost, st)) || (er = sync_st()))
+    return hipfail(er, what);
+  const int n = nloc();
+  std::vector<int32_t> order(n);
+  for (int q = 0; q < n; ++q) order[q] = q;
+  std::stable_sort(order.begin(), order.end(), [&](int x, int y) { return h_cost[x] > h_cost[y]; });
+  // The records of a cached exact M-step group are overwritten here, and the
+  // posteriors' own group must never be taken for one: no reuse on either side.
+  xc_reuse = false;
+  xp_mode = mode;
+  exact_pruned = 0;
+  ms_s1 = ms_fb = 0;
+  int rc;
+  while (true) {  // a capacity overflow restarts the pass; every site is written again
+    xc_groups = 0;
+    xp_ms_fb = xp_ms_sites = 0;
+    if (mode == XP_SWITCH) sw_spilled = 0;
+    rc = estep_split(order, true);
+    if (rc != ESTEP_RESTART) break;
+  }
+  xp_mode = XP_OFF;
+  xc_reuse = false;
+  xp_ms_struct = ms_s1 + ms_fb;  // (ms_fb: the pruned structure re-runs of underflowing individuals)
+  xp_groups = xc_groups;
+  xp_pruned = exact_pruned;
+  ms_s1 = s1_0;
+  ms_fb = fb_0;
+  n_struct_passes = passes_0;
+  exact_pruned = pruned_0;
+  fcap = fcap_0;
+  ccap_mult = ccap_0;
+  rec_words = rec_words_0;
+  h_status = status_0;
+  if ((er = hipMemcpyAsync(d_maxst.p, &maxst_0, 4, hipMemcpyHostToDevice, st)) ||
+      (er = hipMemcpyAsync(d_stamps.p + 20, stamps_0, sizeof stamps_0, hipMemcpyHostToDevice, st)) || (er = sync_st()))
+    return rc ? rc : hipfail(er, what);
+  return rc;
+}
+
 int Ctx::site_posteriors(int32_t *indiv, int32_t *locus, int32_t *status, double *post, const SiteList *pre) {
   if (!have_estep) return fail(HMC_EARG, "genotype posteriors need an E-step first (hmc_resolve_all)");
   // P(genotype) of the last E-step is the divisor: the table must still be the one it ran on
@@ -313,52 +466,7 @@ int Ctx::site_posteriors(int32_t *indiv, int32_t *locus, int32_t *status, double
       (er = hipMemcpyAsync(d_site_locus.p, loc.data(), ns * 4, hipMemcpyHostToDevice, st)) ||
       (er = hipMemsetAsync(d_site_post.p, 0, ns * NP * 8, st)) || (er = hipMemsetAsync(d_site_status.p, 0, ns * 4, st)))
     return hipfail(er, "posteriors");
-  // What the exact-mode structure pass shares with the E-step and a later call
-  // can see is put back afterwards: the last E-step's pass times and counts,
-  // its per-individual status (hmc_get_estep), the frontier statistic and the
-  // structure stamps, and the capacities a restart may have grown.  The stores
-  // (records, traces) are dead between an E-step and the next M- or E-step.
-  const double s1_0 = ms_s1, fb_0 = ms_fb;
-  const int passes_0 = n_struct_passes, pruned_0 = exact_pruned, fcap_0 = fcap, ccap_0 = ccap_mult;
-  const uint64_t rec_words_0 = rec_words;
-  const std::vector<int32_t> status_0 = h_status;
-  uint32_t maxst_0 = 0;
-  unsigned long long stamps_0[20] = {};
-  if ((er = hipMemcpyAsync(&maxst_0, d_maxst.p, 4, hipMemcpyDeviceToHost, st)) ||
-      (er = hipMemcpyAsync(stamps_0, d_stamps.p + 20, sizeof stamps_0, hipMemcpyDeviceToHost, st)) || (er = sync_st()))
-    return hipfail(er, "posteriors");
-  std::vector<int32_t> order(n);
-  for (int q = 0; q < n; ++q) order[q] = q;
-  std::stable_sort(order.begin(), order.end(), [&](int x, int y) { return h_cost[x] > h_cost[y]; });
-  // The records of a cached exact M-step group are overwritten here, and the
-  // posteriors' own group must never be taken for one: no reuse on either side.
-  xc_reuse = false;
-  xp_mode = true;
-  exact_pruned = 0;
-  ms_s1 = ms_fb = 0;
-  int rc;
-  while (true) {  // a capacity overflow restarts the pass; every site is written again
-    xc_groups = 0;
-    xp_ms_fb = xp_ms_sites = 0;
-    rc = estep_split(order, true);
-    if (rc != ESTEP_RESTART) break;
-  }
-  xp_mode = false;
-  xc_reuse = false;
-  xp_ms_struct = ms_s1 + ms_fb;  // (ms_fb: the pruned structure re-runs of underflowing individuals)
-  xp_groups = xc_groups;
-  xp_pruned = exact_pruned;
-  ms_s1 = s1_0;
-  ms_fb = fb_0;
-  n_struct_passes = passes_0;
-  exact_pruned = pruned_0;
-  fcap = fcap_0;
-  ccap_mult = ccap_0;
-  rec_words = rec_words_0;
-  h_status = status_0;
-  if ((er = hipMemcpyAsync(d_maxst.p, &maxst_0, 4, hipMemcpyHostToDevice, st)) ||
-      (er = hipMemcpyAsync(d_stamps.p + 20, stamps_0, sizeof stamps_0, hipMemcpyHostToDevice, st)) || (er = sync_st()))
-    return rc ? rc : hipfail(er, "posteriors");
+  const int rc = xp_pass(XP_GENOTYPE, "posteriors");
   if (rc) return rc;
   if ((status && (er = hipMemcpyAsync(status, d_site_status.p, ns * 4, hipMemcpyDeviceToHost, st))) ||
       (post && (er = hipMemcpyAsync(post, d_site_post.p, ns * NP * 8, hipMemcpyDeviceToHost, st))) || (er = sync_st()))

@@ -1064,4 +1064,152 @@ hipError_t launch_exact_site_posteriors(const ExactArgs &a, const SiteArgs &s, i
   return hipGetLastError();
 }
 
+// Switch posteriors (hmc_switch_posteriors): for every pair (a, b) of
+// consecutive heterozygous loci of an individual, P(the lower-index alleles of
+// a and b lie on the same haplotype | genotype) (cis) and P(on different ones)
+// (trans), each a sum of its own.  One labelled forward sweep per individual
+// (one block each) over the records exact_fb has filled: every state t carries
+// two values g[0][t], g[1][t], the forward likelihood of the paths into t on
+// which the anchor locus's lower allele sits on t's a side (0) or b side (1).
+//   anchor    at record a + 1 (the states carry a's alleles): o(t) = 0 when
+//             the a side holds the lower allele, else 1; g[o(t)][t] = fwd[t],
+//             g[1 - o(t)][t] = 0;
+//   propagate record j from j - 1: over t's contributions r in stored order,
+//             g'[c ^ rev(r)][t] += g[c][state(r)] * tpv[t] — a reversed link
+//             moves the a-side haplotype to the b side (walk_terms); the first
+//             term assigns, later ones add, as exact_fb's forward does;
+//   evaluate  at record b + 1: cis = sum_t g[o(t)][t] bwd[t] / P(genotype),
+//             trans = sum_t g[1 - o(t)][t] bwd[t] / P(genotype); wavefront 0
+//             owns cis, wavefront 1 trans: lane l adds states l, l + 64, ...
+//             ascending, then the fixed butterfly.  Then b becomes the anchor.
+// With head_len > 1 the head record's states carry loci 0 .. head_len - 1 in
+// their two head patterns (a side plo, b side phi): a site inside the head is
+// anchored and evaluated at the head record with no propagation between.
+// The two frontiers (previous and current record, 2 doubles per state each)
+// live in LDS when the individual's largest record has at most `tier` states,
+// else in the block's slice of an HBM scratch: the same doubles in the same
+// order either way.  A state's sums follow its record's contribution order and
+// a site's sums the record's state order, so block size, grid, grouping, shard
+// and tier do not change the bits; no floating-point atomics.
+// Factors are scaled by cancelling powers of two as in exact_site_posteriors.
+__global__ __launch_bounds__(256) void exact_switch_posteriors(ExactArgs a, SwitchArgs s) {
+  extern __shared__ double sw_lds[];  // [2 frontiers][tier states][2 labels]
+  __shared__ int fmx;
+  const int tid = threadIdx.x, NT = blockDim.x;
+  const int lane = tid & (WAVE - 1), wave = tid / WAVE, nw = NT / WAVE;
+  const int L = a.L, hl = a.head_len;
+  for (int q = blockIdx.x; q < a.n_order; q += gridDim.x) {
+    const int bi = a.order[q];
+    const unsigned long long s0 = s.site_off[bi], s1 = s.site_off[bi + 1];
+    if (s0 == s1) continue;
+    const int st0 = a.status[bi];
+    const double pg = a.gprob[bi];
+    const bool resolved = (st0 == EST_OK || st0 == EST_OK_PRUNED) && pg > 0.0 && !isinf(pg);
+    const unsigned long long *roff = a.rec_off + (size_t)bi * (L + 1);
+    const unsigned long long *xo = a.x_off + (size_t)bi * (L + 1);
+    // the individual's largest record (block-uniform after the barrier)
+    int fbig = 0;
+    if (resolved) {
+      __syncthreads();  // every thread has read the previous individual's maximum
+      if (tid == 0) fmx = 0;
+      __syncthreads();
+      int f = 0;
+      for (int j = hl + tid; j <= L; j += NT) f = max(f, (int)a.rec[roff[j]]);
+      atomicMax(&fmx, f);
+      __syncthreads();
+      fbig = fmx;
+    }
+    const bool in_lds = fbig <= s.tier;
+    // (a frontier neither store holds cannot occur: the host sizes the scratch from the group's fmax)
+    const bool fits = in_lds || (s.scratch && fbig <= s.scratch_states);
+    if (!resolved || pg < SITE_PG_MIN || !fits) {  // rows of zeros: unresolved (1), or P(genotype) subnormal (2)
+      for (unsigned long long i = s0 * 2 + tid; i < s1 * 2; i += NT) s.post[i] = 0.0;
+      for (unsigned long long i = s0 + tid; i < s1; i += NT) s.site_status[i] = resolved && fits ? 2 : 1;
+      continue;
+    }
+    const size_t cap = in_lds ? (size_t)s.tier : (size_t)s.scratch_states;
+    double *cur = in_lds ? sw_lds : s.scratch + (size_t)blockIdx.x * 4 * cap;
+    double *prev = cur + 2 * cap;
+    const int sc = -ilogb(pg), sa = sc / 2, sb = sc - sa;
+    const double pgs = ldexp(pg, sc);
+    // o(t): the side of state t of record j that carries the lower allele of locus k
+    // (k < head_len: j is the head record; its hdr word carries locus 0 when head_len is 1)
+    auto low_side = [&](const RecView &R, int k, int t) -> int {
+      uint32_t xa, xb;
+      if (k < hl && hl > 1) {
+        const uint32_t *plo = R.cb + R.F + 1, *phi = plo + R.F;
+        xa = a.head_al[(size_t)plo[t] * hl + k];
+        xb = a.head_al[(size_t)phi[t] * hl + k];
+      } else {
+        const uint32_t h = R.hdr[t];
+        xa = h & 0xFFu;
+        xb = (h >> 8) & 0xFFu;
+      }
+      return xa < xb ? 0 : 1;
+    };
+    auto anchor = [&](int j, int k) {
+      const RecView R(a.rec + roff[j], j == hl);
+      const double *fw = (const double *)(a.x + xo[j]);
+      for (int t = tid; t < R.F; t += NT) {
+        const int o = low_side(R, k, t);
+        cur[2 * t + o] = fw[t];
+        cur[2 * t + (o ^ 1)] = 0.0;
+      }
+      __syncthreads();
+    };
+    int j = s.locus_a[s0] < hl ? hl : s.locus_a[s0] + 1;
+    __syncthreads();  // the previous individual's last readers of the frontiers are done
+    anchor(j, s.locus_a[s0]);
+    for (unsigned long long site = s0; site < s1; ++site) {
+      const int kb = s.locus_b[site];
+      const int jb = kb < hl ? hl : kb + 1;
+      while (j < jb) {  // record j + 1 from record j (j + 1 > head_len: never the head record)
+        ++j;
+        double *x = prev;
+        prev = cur;
+        cur = x;
+        const RecView R(a.rec + roff[j], false);
+        for (int t = tid; t < R.F; t += NT) {
+          const double tpv = R.tpv[t];
+          double n0 = 0.0, n1 = 0.0;
+          const uint32_t r0 = R.cb[t], r1 = R.cb[t + 1];
+          for (uint32_t r = r0; r < r1; ++r) {
+            const uint32_t w = R.ct[r];
+            const uint32_t sp = cw_state(w), rv = cw_rev(w) ? 1u : 0u;
+            const double v0 = prev[2 * sp + rv] * tpv, v1 = prev[2 * sp + (rv ^ 1u)] * tpv;
+            n0 = r == r0 ? v0 : n0 + v0;
+            n1 = r == r0 ? v1 : n1 + v1;
+          }
+          cur[2 * t] = n0;
+          cur[2 * t + 1] = n1;
+        }
+        __syncthreads();
+      }
+      {
+        const RecView R(a.rec + roff[j], j == hl);
+        const double *bw = (const double *)(a.x + xo[j]) + R.F;
+        for (int w = wave; w < 2; w += nw) {  // wave-uniform: 0 cis, 1 trans
+          double part[1] = {0.0};
+          for (int t = lane; t < R.F; t += WAVE)
+            part[0] += ldexp(cur[2 * t + (low_side(R, kb, t) ^ w)], sa) * ldexp(bw[t], sb);
+          const double v = group_sum_fixed<WAVE>(part) / pgs;
+          if (lane == 0) s.post[site * 2 + w] = v;
+        }
+        if (tid == 0) s.site_status[site] = 0;
+      }
+      __syncthreads();  // the sums have read the frontier the next anchor overwrites
+      if (site + 1 < s1) anchor(j, kb);
+    }
+  }
+}
+
+hipError_t launch_exact_switch_posteriors(const ExactArgs &a, const SwitchArgs &s, int grid, hipStream_t st, int block) {
+  if (a.n_order <= 0) return hipSuccess;
+  if (block < WAVE || block > 256 || block % WAVE || grid < 1 || s.tier < 1 || s.tier > SWITCH_TIER_MAX || !s.site_off ||
+      !s.locus_a || !s.locus_b || !s.post || !s.site_status || (s.scratch && s.scratch_states < 1))
+    return hipErrorInvalidValue;
+  hipLaunchKernelGGL(exact_switch_posteriors, dim3(grid), dim3(block), (size_t)s.tier * 32, st, a, s);
+  return hipGetLastError();
+}
+
 }  // namespace hmc

@@ -104,4 +104,23 @@ constexpr double SITE_PG_MIN = 2.2250738585072014e-308;  // DBL_MIN: below it th
 // after exact_fb over the same group; any block size that is a multiple of 64 gives the same bits
 hipError_t launch_exact_site_posteriors(const ExactArgs &a, const SiteArgs &s, int grid, hipStream_t st, int block = 256);
 
+// Switch posteriors (exact_switch_posteriors): an individual's sites are the
+// pairs of consecutive heterozygous loci (both input alleles present and
+// different), as a CSR over batch indices with locus_a ascending, so that
+// locus_b of a site is locus_a of the individual's next one; one output row
+// (cis, trans) per site.
+struct SwitchArgs {
+  const unsigned long long *site_off = nullptr;  // [batch + 1]
+  const int32_t *locus_a = nullptr, *locus_b = nullptr;  // [sites]
+  double *post = nullptr;                        // [sites][2]
+  int32_t *site_status = nullptr;                // [sites] as SiteArgs::site_status
+  int tier = 0;                                  // states per record whose two label frontiers the LDS holds (32 B per state)
+  double *scratch = nullptr;                     // [grid][4 scratch_states]: the frontiers of individuals past the tier
+  int scratch_states = 0;                        // the group's fmax when scratch is given
+};
+constexpr int SWITCH_TIER_DEFAULT = 1024;  // 32 KiB of LDS: four blocks to a compute unit
+constexpr int SWITCH_TIER_MAX = 2032;      // with the kernel's static LDS within the 64 KiB a launch gets unasked
+// after exact_fb over the same group; block sizes 64, 128, 192 and 256 give the same bits
+hipError_t launch_exact_switch_posteriors(const ExactArgs &a, const SwitchArgs &s, int grid, hipStream_t st, int block = 256);
+
 }  // namespace hmc

@@ -512,6 +512,50 @@ class HaploModel:
         """genotype_posteriors as text, one line per site and non-zero pair (hmc_write_posteriors)."""
         self._check(lib().hmc_write_posteriors(self._h, path.encode()))
 
+    def switch_posterior_shape(self) -> tuple[int, int]:
+        """(sites of this rank's shard, 2) of switch_posteriors, counted from
+        the panel without device work; no model is needed."""
+        ns = C.c_int64()
+        self._check(lib().hmc_switch_posteriors(self._h, C.byref(ns), None, None, None, None, None))
+        return ns.value, 2
+
+    def switch_posteriors(self) -> dict:
+        """Phase confidence between consecutive heterozygous loci under the
+        model of the last resolve_all (hmc_switch_posteriors).  A site is a
+        pair (locus_a, locus_b) of consecutive loci at which the individual's
+        two input alleles are present and differ: indiv[n], locus_a[n],
+        locus_b[n], status[n] (0 ok; rows of zeros: 1 individual unresolved,
+        2 its P(genotype) subnormal) and post[n][2] = (cis, trans): the
+        probability that the lower-index alleles (allele_table()) of the two
+        loci lie on the same haplotype, and on different ones."""
+        ns, _ = self.switch_posterior_shape()
+        out = dict(indiv=np.zeros(ns, np.int32), locus_a=np.zeros(ns, np.int32), locus_b=np.zeros(ns, np.int32),
+                   status=np.zeros(ns, np.int32), post=np.zeros((ns, 2), np.float64))
+        n2 = C.c_int64()
+        self._check(lib().hmc_switch_posteriors(self._h, C.byref(n2), _p(out["indiv"], C.c_int32),
+                                                _p(out["locus_a"], C.c_int32), _p(out["locus_b"], C.c_int32),
+                                                _p(out["status"], C.c_int32), _p(out["post"], C.c_double)))
+        assert n2.value == ns
+        return out
+
+    def switch_stats(self) -> dict:
+        """Device ms and counts of the last switch_posteriors (hmc_last_switch_stats)."""
+        s, f, k = C.c_double(), C.c_double(), C.c_double()
+        g, p, sp = C.c_int(), C.c_int(), C.c_int()
+        self._check(lib().hmc_last_switch_stats(self._h, C.byref(s), C.byref(f), C.byref(k), C.byref(g), C.byref(p),
+                                                C.byref(sp)))
+        return dict(structure_ms=s.value, fb_ms=f.value, sweep_ms=k.value, groups=g.value, n_pruned=p.value,
+                    n_spilled=sp.value)
+
+    def set_switch_tier(self, states: int = 0):
+        """States per locus the switch sweep keeps in LDS (0 = default); larger
+        frontiers go through device memory.  Results do not depend on it."""
+        self._check(lib().hmc_set_switch_tier(self._h, int(states)))
+
+    def write_switch_posteriors(self, path: str):
+        """switch_posteriors as text, one line per site of status 0 (hmc_write_switch_posteriors)."""
+        self._check(lib().hmc_write_switch_posteriors(self._h, path.encode()))
+
     def timings(self) -> dict:
         f, t, m = C.c_double(), C.c_double(), C.c_double()
         self._check(lib().hmc_last_timings(self._h, C.byref(f), C.byref(t), C.byref(m)))

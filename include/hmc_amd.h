@@ -278,6 +278,40 @@ int hmc_genotype_posteriors(hmc_ctx *ctx, int64_t *n_sites, int *n_pairs, int32_
 int hmc_last_posterior_stats(const hmc_ctx *ctx, double *structure_ms, double *fb_ms, double *sites_ms, int *groups,
                              int *n_pruned);
 
+/* Switch posteriors: how sure the phase is between consecutive heterozygous
+ * loci.  For an individual let h1 < h2 < ... be the loci where both input
+ * alleles are present and differ; its sites are the pairs (locus_a, locus_b) =
+ * (h_q, h_q+1) (the loci between are homozygous or have a missing allele).
+ * post[site][0] (cis) = P(the allele of lower allele-table index at locus_a
+ * and the one of lower index at locus_b lie on the same haplotype | genotype)
+ * under the current model, post[site][1] (trans) the same for different
+ * haplotypes (indices as in hmc_allele_table).  Both are exact sums of forward
+ * x backward likelihood over the lattice states, with no k-best cut and no
+ * sampling, and each is a sum of its own: a row of status 0 sums to 1 up to
+ * rounding.  Needs a preceding hmc_resolve_all (any E-step mode); runs its own
+ * forward-backward pass and changes no later result.  With indiv, locus_a,
+ * locus_b, status and post all NULL the call only counts: *n_sites from the
+ * panel, no device work and no model needed.  Otherwise (any of the five may
+ * be NULL) sites of this rank's shard come individual-major with locus_a
+ * ascending: indiv[n_sites] (panel index), locus_a[n_sites], locus_b[n_sites],
+ * status[n_sites], post[n_sites][2].  status as for hmc_genotype_posteriors:
+ * 0 ok; 1 the individual is unresolved; 2 its P(genotype) is below DBL_MIN;
+ * rows of status 1 and 2 are zeros.  A site with locus_a below head_len of an
+ * individual with a missing allele at a head locus comes from the reference's
+ * head pairing, which is not a phasing model: only the normalisation holds.
+ * HMC_EARG when no E-step has run or the model has changed since the last one;
+ * HMC_EUNSUPPORTED as for hmc_genotype_posteriors.  The bits do not depend on
+ * launch shapes, store budgets, sharding or hmc_set_switch_tier.
+ * Replaces no reference interface. */
+int hmc_switch_posteriors(hmc_ctx *ctx, int64_t *n_sites, int32_t *indiv, int32_t *locus_a, int32_t *locus_b, int32_t *status,
+                          double *post);
+/* Last hmc_switch_posteriors: device ms of its structure passes, of the
+ * forward-backward kernel and of the labelled forward sweep; groups the
+ * individuals ran in; individuals on pruned records; individuals whose largest
+ * frontier exceeded the sweep's LDS tier and went through device memory.
+ * Replaces no reference interface. */
+int hmc_last_switch_stats(const hmc_ctx *ctx, double *structure_ms, double *fb_ms, double *sweep_ms, int *groups,
+                          int *n_pruned, int *n_spilled);
 /* ---- whole EM: HaploModel::run (HaploModel.cpp:117-155) ------------------ */
 typedef struct hmc_iter_log {
   double log_likelihood;
@@ -368,6 +402,14 @@ int hmc_write_patterns(hmc_ctx *ctx, const char *path);
  * model of that last E-step.  Replaces no reference interface. */
 int hmc_write_posteriors(hmc_ctx *ctx, const char *path);
 
+/* hmc_switch_posteriors as text (hmc_resolve --output-switch-posteriors): the
+ * header "Id\tMarkerA\tMarkerB\tAlleleA\tAlleleB\tCis\tTrans", then one line
+ * per site of status 0 in the call's site order: individual id, the two marker
+ * names, the lower-index allele's symbol at each of the two loci as the
+ * genotype files spell them, cis and trans as %.17g (they read back to the
+ * same doubles).  Needs a preceding hmc_resolve_all or hmc_run.
+ * Replaces no reference interface. */
+int hmc_write_switch_posteriors(hmc_ctx *ctx, const char *path);
 /* ---- tuning -------------------------------------------------------------- */
 /* frontier_cap: initial states per locus and individual (doubles on
  * overflow, at most 2 097 151); trace_bytes: trace-store budget (0 =
@@ -397,6 +439,13 @@ int hmc_set_pass_shapes(hmc_ctx *ctx, int structure_waves, int structure_ipc, in
  * store (min(28 %, 80 GiB); 0 with a trace budget given = the same number).
  * Individuals pass in groups whose records and traces fit them. */
 int hmc_set_store_budgets(hmc_ctx *ctx, uint64_t trace_bytes, uint64_t record_bytes);
+/* States per locus whose two label frontiers hmc_switch_posteriors keeps in
+ * LDS (32 bytes per state); an individual with a larger frontier at any locus
+ * goes through a device-memory scratch instead.  0 = the default (1 024);
+ * HMC_EARG above 2 032, the most a workgroup's 64 KiB holds.  Results do not
+ * depend on it (it lets small panels take the device-memory path).
+ * Replaces no reference interface. */
+int hmc_set_switch_tier(hmc_ctx *ctx, int states);
 /* E-step implementation: 0 (default) = two passes, a structure pass that
  * replays extendAll/addHaploPair (HaploBuilder.cpp:226-261) on pattern ids
  * and a value pass with the k-best lists; individuals whose forward

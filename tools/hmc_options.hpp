@@ -14,7 +14,7 @@ struct Options {
   std::vector<std::string> files;
   std::string model = "MV", format = "PHASE";
   int mc_order = 1, num_patterns = -1;
-  bool exact = false, output_patterns = false, output_posteriors = false;
+  bool exact = false, output_patterns = false, output_posteriors = false, output_switch_posteriors = false;
 };
 
 // --output-posteriors (no reference counterpart): <first file>.posteriors, the
@@ -37,7 +37,10 @@ constexpr const char *USAGE =
     "  --device D            GPU index (default 0)\n"
     "  -d, --debug LEVEL     accepted and ignored\n"
     "  --output-posteriors   write <datafile>.posteriors: genotype posteriors at missing loci under the\n"
-    "                        final model (the model of the last E-step of the run)";
+    "                        final model (the model of the last E-step of the run)\n"
+    "  --output-switch-posteriors  write <datafile>.switches: for every pair of consecutive heterozygous\n"
+    "                        loci of an individual, the probability that their lower alleles share a\n"
+    "                        haplotype (cis) and that they do not (trans), under the final model";
 
 // 0 on success; otherwise `err` says what is wrong (a missing value, an
 // unknown option, no data file).
@@ -65,6 +68,7 @@ inline int parse_options(int argc, const char *const *argv, Options &o, std::str
     else if (a == "--exact-estimate") o.exact = true;                                      // HMC.cpp:42
     else if (a == "--output-patterns") { if (!next()) return 1; o.output_patterns = true; }  // HMC.cpp:30, 229-232
     else if (a == "--output-posteriors") o.output_posteriors = true;
+    else if (a == "--output-switch-posteriors") o.output_switch_posteriors = true;
     else if (a == "-m" || a == "--model") { if (!next()) return 1; o.model = v; }          // HMC.cpp:35
     else if (a == "-o" || a == "--mc-order") { if (!next()) return 1; o.mc_order = atoi(v); }      // HMC.cpp:41
     else if (a == "-n" || a == "--num-patterns") { if (!next()) return 1; o.num_patterns = atoi(v); }  // HMC.cpp:38

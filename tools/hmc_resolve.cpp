@@ -10,10 +10,13 @@
 //   hmc_resolve [-f PHASE|HPM|HPM2|BENCH2|BENCH3] [-a 1.5] [-r min_freq] [-n num]
 //               [-m MV|MC|MA] [-o mc_order] [--exact-estimate] [-i 1]
 //               [--sample-size 10] [--min-pattern-len 1] [--max-pattern-len 30]
-//               [--output-patterns x] [--output-posteriors] [--device 0] datafile ...
+//               [--output-patterns x] [--output-posteriors] [--output-switch-posteriors]
+//               [--device 0] datafile ...
 // --output-posteriors (no reference counterpart) writes <first file>.posteriors:
 // genotype posteriors at the loci with a missing input allele, under the final
-// model (hmc_write_posteriors).
+// model (hmc_write_posteriors).  --output-switch-posteriors (none either)
+// writes <first file>.switches: cis and trans posteriors between consecutive
+// heterozygous loci under the same model (hmc_write_switch_posteriors).
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -83,6 +86,10 @@ int main(int argc, char **argv) {
   if (o.output_posteriors) {  // of the run's last E-step: hmc_run ends on an E-step of the final model
     const std::string qf = files[0] + ".posteriors";
     if ((rc = hmc_write_posteriors(ctx, qf.c_str()))) die("hmc_write_posteriors");
+  }
+  if (o.output_switch_posteriors) {  // of the same E-step
+    const std::string sf = files[0] + ".switches";
+    if ((rc = hmc_write_switch_posteriors(ctx, sf.c_str()))) die("hmc_write_switch_posteriors");
   }
   hmc_ctx_destroy(ctx);
   return 0;
