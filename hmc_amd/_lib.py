@@ -86,6 +86,10 @@ _SIGS = [
     ("hmc_switch_posteriors", _i, [_vp, _P(C.c_int64), _P(C.c_int32), _P(C.c_int32), _P(C.c_int32), _P(C.c_int32), _P(_d)]),
     ("hmc_last_switch_stats", _i, [_vp, _P(_d), _P(_d), _P(_d), _P(_i), _P(_i), _P(_i)]),
     ("hmc_set_switch_tier", _i, [_vp, _i]),
+    ("hmc_pair_posteriors", _i, [_vp, C.c_int64, _P(C.c_int32), _P(C.c_int32), _P(C.c_int32), _P(C.c_int32), _P(_d)]),
+    ("hmc_pair_span_list", _i, [_vp, _i, _P(C.c_int64), _P(C.c_int32), _P(C.c_int32), _P(C.c_int32)]),
+    ("hmc_last_pair_stats", _i, [_vp, _P(_d), _P(_d), _P(_d), _P(_i), _P(_i), _P(_i), _P(_i), _P(_i)]),
+    ("hmc_set_pair_tuning", _i, [_vp, _i, _i]),
     ("hmc_clear_samples", _i, [_vp]),
     ("hmc_run", _i, [_vp, _i, _P(IterLog), _i, _P(_i), _P(_d), _P(_u64), _P(_i)]),
     ("hmc_em_iteration", _i, [_vp, _i, _i, _i, _P(_d), _P(IterLog), _P(_i)]),
@@ -106,6 +110,7 @@ _SIGS = [
     ("hmc_write_phase", _i, [_vp, _cp]),
     ("hmc_write_posteriors", _i, [_vp, _cp]),
     ("hmc_write_switch_posteriors", _i, [_vp, _cp]),
+    ("hmc_write_pair_posteriors", _i, [_vp, _cp, _i]),
     ("hmc_set_tuning", _i, [_vp, _i, _u64, _i]),
     ("hmc_set_estep_shape", _i, [_vp, _i, _i]),
     ("hmc_set_pass_shapes", _i, [_vp, _i, _i, _i, _i]),

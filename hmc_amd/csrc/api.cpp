@@ -939,6 +939,54 @@ int hmc_set_switch_tier(hmc_ctx *h, int states) {
   return HMC_OK;
 }
 
+int hmc_pair_posteriors(hmc_ctx *h, int64_t n, const int32_t *indiv, const int32_t *locus_a, const int32_t *locus_b,
+                        int32_t *status, double *post) {
+  if (!h) return HMC_EARG;
+  Ctx &c = h->c;
+  if (!c.have_panel) return c.fail(HMC_EARG, "no panel loaded");
+  return c.pair_posteriors(n, indiv, locus_a, locus_b, status, post);
+}
+
+int hmc_pair_span_list(hmc_ctx *h, int span, int64_t *n, int32_t *indiv, int32_t *locus_a, int32_t *locus_b) {
+  if (!h) return HMC_EARG;
+  Ctx &c = h->c;
+  if (!c.have_panel) return c.fail(HMC_EARG, "no panel loaded");
+  if (span < 1) return c.fail(HMC_EARG, "pair span list: span %d is below 1", span);
+  std::vector<int32_t> qi, qa, qb;
+  c.pair_span_list(span, qi, qa, qb);
+  if (n) *n = (int64_t)qi.size();
+  if (indiv) std::copy(qi.begin(), qi.end(), indiv);
+  if (locus_a) std::copy(qa.begin(), qa.end(), locus_a);
+  if (locus_b) std::copy(qb.begin(), qb.end(), locus_b);
+  return HMC_OK;
+}
+
+int hmc_last_pair_stats(const hmc_ctx *h, double *structure_ms, double *fb_ms, double *sweep_ms, int *groups, int *n_pruned,
+                        int *n_spilled, int *slots, int *max_rounds) {
+  if (!h) return HMC_EARG;
+  if (structure_ms) *structure_ms = h->c.pr_ms_struct;
+  if (fb_ms) *fb_ms = h->c.pr_ms_fb;
+  if (sweep_ms) *sweep_ms = h->c.pr_ms_sweep;
+  if (groups) *groups = h->c.pr_groups;
+  if (n_pruned) *n_pruned = h->c.pr_pruned;
+  if (n_spilled) *n_spilled = h->c.pr_spilled;
+  if (slots) *slots = h->c.pr_ns;
+  if (max_rounds) *max_rounds = h->c.pr_rounds;
+  return HMC_OK;
+}
+
+int hmc_set_pair_tuning(hmc_ctx *h, int slots, int tier_states) {
+  if (!h) return HMC_EARG;
+  if (slots != 0 && !hmc::pair_slots_ok(slots))
+    return h->c.fail(HMC_EARG, "pair tuning: %d slots are not instantiated (1, 2, 4 or 8; 0 = automatic)", slots);
+  if (tier_states < 0 || tier_states > hmc::pair_tier_max(hmc::PAIR_SLOTS_MAX))
+    return h->c.fail(HMC_EARG, "pair tuning: a tier of %d states is outside [0, %d]", tier_states,
+                     hmc::pair_tier_max(hmc::PAIR_SLOTS_MAX));
+  h->c.pr_slots = slots;
+  h->c.pr_tier = tier_states;
+  return HMC_OK;
+}
+
 int hmc_run(hmc_ctx *h, int max_iteration, hmc_iter_log *log, int log_cap, int *iterations, double *t_m0_s,
             uint64_t *r_m0, int *n_patterns0) {
   if (!h) return HMC_EARG;
@@ -1074,6 +1122,39 @@ int hmc_write_switch_posteriors(hmc_ctx *h, const char *path) {
     fprintf(fp, "%s\t%s\t%s", d.ids[indiv[q]].c_str(), d.names[ka].c_str(), d.names[kb].c_str());
     put_lower(indiv[q], ka);
     put_lower(indiv[q], kb);
+    fprintf(fp, "\t%.17g\t%.17g\n", post[2 * q], post[2 * q + 1]);
+  }
+  const bool bad = ferror(fp) != 0;
+  if (fclose(fp) != 0 || bad) return c.fail(HMC_EIO, "Can not write file %s!", path);
+  return HMC_OK;
+}
+
+int hmc_write_pair_posteriors(hmc_ctx *h, const char *path, int span) {
+  if (!h || !path || !h->c.have_panel) return HMC_EARG;
+  Ctx &c = h->c;
+  if (span < 1) return c.fail(HMC_EARG, "pair posteriors: span %d is below 1", span);
+  std::vector<int32_t> indiv, la, lb;
+  c.pair_span_list(span, indiv, la, lb);
+  const size_t ns = indiv.size();
+  std::vector<int32_t> status(ns);
+  std::vector<double> post(ns * 2);
+  int rc;
+  if ((rc = c.pair_posteriors((int64_t)ns, indiv.data(), la.data(), lb.data(), status.data(), post.data()))) return rc;
+  FILE *fp = fopen(path, "w");
+  if (!fp) return c.fail(HMC_EIO, "Can not open file %s!", path);
+  const hmc::FileData d = writer_meta(c);
+  fprintf(fp, "Id\tMarkerA\tMarkerB\tAlleleA\tAlleleB\tCis\tTrans\n");
+  auto put_lower = [&](int i, int k) {  // the lower-index allele of the two, as the genotype files spell alleles
+    const uint8_t *g0 = c.pan.idx.data() + ((size_t)i * 2) * c.pan.L, *g1 = g0 + c.pan.L;
+    const int32_t a = c.pan.symbol(k, std::min(g0[k], g1[k]));
+    if (c.pan.types[k] == 'S') fprintf(fp, "\t%c", (char)a);
+    else fprintf(fp, "\t%d", a);
+  };
+  for (size_t q = 0; q < ns; ++q) {
+    if (status[q] != 0) continue;
+    fprintf(fp, "%s\t%s\t%s", d.ids[indiv[q]].c_str(), d.names[la[q]].c_str(), d.names[lb[q]].c_str());
+    put_lower(indiv[q], la[q]);
+    put_lower(indiv[q], lb[q]);
     fprintf(fp, "\t%.17g\t%.17g\n", post[2 * q], post[2 * q + 1]);
   }
   const bool bad = ferror(fp) != 0;

@@ -20,6 +20,7 @@
 #include <map>
 #include <string>
 #include <thread>
+#include <tuple>
 #include <vector>
 
 #include "../../include/hmc_amd.h"
@@ -808,7 +809,7 @@ struct Ctx {
   void site_list(SiteList &sl) const;
   int site_group(const ExactArgs &x, int k, int dev_cu);
   // what the exact group runs after exact_fb in place of the trie walk
-  enum XpMode { XP_OFF = 0, XP_GENOTYPE = 1, XP_SWITCH = 2 };
+  enum XpMode { XP_OFF = 0, XP_GENOTYPE = 1, XP_SWITCH = 2, XP_PAIR = 3 };
   XpMode xp_mode = XP_OFF;
   // The part the two posterior calls share: every individual of the shard
   // through estep_split(order, true) with xp_mode = mode, and whatever that
@@ -832,6 +833,35 @@ struct Ctx {
   double sw_ms_struct = 0, sw_ms_fb = 0, sw_ms_sweep = 0;
   int sw_groups = 0, sw_pruned = 0, sw_spilled = 0;
   size_t n_switch_last = 0;
+  // Pair posteriors (hmc_pair_posteriors): caller-given queries (individual,
+  // locus a < locus b, both heterozygous in the input), any distance apart;
+  // exact_pair_posteriors per group (XP_PAIR).  The schedule is built on the
+  // host: an individual's distinct queries sorted by (a, b) are its rows, its
+  // distinct anchors a take the interval [a, largest b] and a slot by greedy
+  // interval colouring in anchor order (the lowest free of NS, else the first
+  // later round with one), and the kernel gets the events in execution order.
+  struct PairPlan {
+    std::vector<unsigned long long> row_off, ev_off;  // [n + 1] over the shard's individuals
+    std::vector<int32_t> row_a, row_b;                // the distinct queries, individual-major, (a, b) ascending
+    std::vector<size_t> row_of;                       // [queries] the row that answers the caller's query
+    std::vector<PairEvent> ev;
+    int need = 0, rounds = 0;  // most anchors live at once, most rounds, of any individual
+  };
+  // 0, or HMC_EARG with a message naming the first offending query
+  int pair_plan(int64_t nq, const int32_t *indiv, const int32_t *locus_a, const int32_t *locus_b, int ns, PairPlan &pl);
+  int pair_posteriors(int64_t nq, const int32_t *indiv, const int32_t *locus_a, const int32_t *locus_b, int32_t *status,
+                      double *post);
+  // (h_q, h_q+d), 1 <= d <= span, over the shard: individual-major, a ascending, then b
+  void pair_span_list(int span, std::vector<int32_t> &indiv, std::vector<int32_t> &locus_a, std::vector<int32_t> &locus_b) const;
+  int pair_group(const ExactArgs &x, const int32_t *ids, const std::vector<int32_t> &fm, int k, int dev_cu);
+  DevBuf<unsigned long long> d_pr_evoff;
+  DevBuf<PairEvent> d_pr_ev;
+  DevBuf<double> d_pr_scratch;
+  int pr_slots = 0, pr_tier = 0;  // hmc_set_pair_tuning (0: automatic)
+  int pr_ns_run = 0;              // NS of the running call
+  // of the last call, as sw_* above; pr_ns: the NS used, pr_rounds: most rounds of any individual
+  double pr_ms_struct = 0, pr_ms_fb = 0, pr_ms_sweep = 0;
+  int pr_groups = 0, pr_pruned = 0, pr_spilled = 0, pr_ns = 0, pr_rounds = 0;
   DevBuf<unsigned long long> d_site_off;
   DevBuf<int32_t> d_site_locus, d_site_status;
   DevBuf<double> d_site_post;

@@ -251,6 +251,7 @@ int Ctx::exact_group(const int32_t *ids, int k, const std::function<int(std::vec
   ++xc_groups;
   if (xp_mode == XP_GENOTYPE) return site_group(x, k, dev_cu);  // genotype posteriors: no trie, no walk
   if (xp_mode == XP_SWITCH) return switch_group(x, ids, fm, k, dev_cu);
+  if (xp_mode == XP_PAIR) return pair_group(x, ids, fm, k, dev_cu);
   return exact_walk_group(x, k, dev_cu);
 }
 
@@ -353,6 +354,232 @@ int Ctx::switch_posteriors(int32_t *indiv, int32_t *locus_a, int32_t *locus_b, i
   return HMC_OK;
 }
 
+int Ctx::pair_group(const ExactArgs &x, const int32_t *ids, const std::vector<int32_t> &fm, int k, int dev_cu) {
+  const int NS = pr_ns_run;
+  PairArgs s;
+  s.row_off = d_site_off.p;
+  s.ev_off = d_pr_evoff.p;
+  s.ev = d_pr_ev.p;
+  s.post = d_site_post.p;
+  s.row_status = d_site_status.p;
+  s.tier = pr_tier > 0 ? pr_tier : PAIR_TIER_DEFAULT;
+  s.lds_states = std::max(1, std::min(s.tier, x.fmax));  // no more LDS than the group's largest record asks for
+  int grid = std::max(1, std::min(k, dev_cu * 8));
+  hipError_t e;
+  int spilled = 0;
+  for (int q = 0; q < k; ++q) spilled += fm[ids[q]] > s.tier;
+  pr_spilled += spilled;
+  if (spilled) {  // frontiers past the tier: 32 NS B per state and block in HBM, at most 1 GiB (the grid does not change the bits)
+    grid = (int)std::max<size_t>(1, std::min<size_t>((size_t)grid, ((size_t)1 << 30) / ((size_t)32 * NS * x.fmax)));
+    if ((e = d_pr_scratch.ensure((size_t)grid * 4 * NS * x.fmax))) return hipfail(e, "exact_pair_posteriors");
+    s.scratch = d_pr_scratch.p;
+    s.scratch_states = x.fmax;
+  }
+  hipEventRecord(ev[0], st);
+  if ((e = launch_exact_pair_posteriors(x, s, NS, grid, st))) return hipfail(e, "exact_pair_posteriors");
+  hipEventRecord(ev[1], st);
+  if ((e = sync_st())) return hipfail(e, "exact_pair_posteriors");
+  float ms = 0;
+  hipEventElapsedTime(&ms, ev[0], ev[1]);
+  xp_ms_sites += ms;
+  return HMC_OK;
+}
+
+void Ctx::pair_span_list(int span, std::vector<int32_t> &indiv, std::vector<int32_t> &locus_a,
+                         std::vector<int32_t> &locus_b) const {
+  const int n = nloc(), L = pan.L;
+  indiv.clear();
+  locus_a.clear();
+  locus_b.clear();
+  std::vector<int32_t> het;
+  for (int i = 0; i < n; ++i) {
+    const uint8_t *g0 = pan.idx.data() + ((size_t)(i0 + i) * 2) * L, *g1 = g0 + L;
+    het.clear();
+    for (int k = 0; k < L; ++k)
+      if (g0[k] != MISSING && g1[k] != MISSING && g0[k] != g1[k]) het.push_back(k);
+    for (size_t q = 0; q < het.size(); ++q)
+      for (size_t d = 1; d <= (size_t)span && q + d < het.size(); ++d) {
+        indiv.push_back(i0 + i);
+        locus_a.push_back(het[q]);
+        locus_b.push_back(het[q + d]);
+      }
+  }
+}
+
+int Ctx::pair_plan(int64_t nq, const int32_t *indiv, const int32_t *locus_a, const int32_t *locus_b, int ns, PairPlan &pl) {
+  const int n = nloc(), L = pan.L, hl = head_len;
+  for (int64_t q = 0; q < nq; ++q) {
+    const int i = indiv[q], a = locus_a[q], b = locus_b[q];
+    if (i < i0 || i >= i1)
+      return fail(HMC_EARG, "pair posteriors: query %lld: individual %d is outside this rank's shard [%d, %d)", (long long)q, i,
+                  i0, i1);
+    if (a < 0 || a >= L || b < 0 || b >= L)
+      return fail(HMC_EARG, "pair posteriors: query %lld: loci (%d, %d) outside [0, %d)", (long long)q, a, b, L);
+    if (a >= b) return fail(HMC_EARG, "pair posteriors: query %lld: locus_a %d is not below locus_b %d", (long long)q, a, b);
+    const uint8_t *g0 = pan.idx.data() + ((size_t)i * 2) * L, *g1 = g0 + L;
+    for (int k : {a, b})
+      if (g0[k] == MISSING || g1[k] == MISSING || g0[k] == g1[k])
+        return fail(HMC_EARG, "pair posteriors: query %lld: locus %d of individual %d is not heterozygous in the input",
+                    (long long)q, k, i);
+  }
+  // the caller's queries sorted by (individual, a, b); the distinct ones are the rows
+  std::vector<size_t> ord((size_t)nq);
+  for (size_t q = 0; q < ord.size(); ++q) ord[q] = q;
+  auto key_less = [&](size_t x, size_t y) {
+    if (indiv[x] != indiv[y]) return indiv[x] < indiv[y];
+    if (locus_a[x] != locus_a[y]) return locus_a[x] < locus_a[y];
+    return locus_b[x] < locus_b[y];
+  };
+  std::sort(ord.begin(), ord.end(), key_less);
+  pl.row_off.assign((size_t)n + 1, 0);
+  pl.ev_off.assign((size_t)n + 1, 0);
+  pl.row_a.clear();
+  pl.row_b.clear();
+  pl.row_of.assign((size_t)nq, 0);
+  pl.ev.clear();
+  pl.need = pl.rounds = 0;
+  auto rec_of = [&](int k) { return k < hl ? hl : k + 1; };
+  struct Anchor {
+    int a, ja, jend, round, slot;
+    size_t r0, r1;  // its rows
+  };
+  struct Keyed {  // execution order within a round (exact.hpp, PairEvent)
+    int rec, phase, a, kind, b;
+    PairEvent ev;
+  };
+  std::vector<Anchor> anchors;
+  std::vector<std::vector<int>> busy;  // [round][slot]: the record at which the slot's holder is freed
+  std::vector<int> ends;               // the intervals' last records, for the number of anchors live at once
+  std::vector<Keyed> evs;
+  size_t p = 0;
+  for (int i = 0; i < n; ++i) {
+    const size_t row0 = pl.row_a.size();
+    anchors.clear();
+    for (; p < ord.size() && indiv[ord[p]] == i0 + i; ++p) {
+      const int a = locus_a[ord[p]], b = locus_b[ord[p]];
+      if (pl.row_a.size() == row0 || pl.row_a.back() != a || pl.row_b.back() != b) {
+        pl.row_a.push_back(a);
+        pl.row_b.push_back(b);
+        if (anchors.empty() || anchors.back().a != a) anchors.push_back({a, rec_of(a), 0, 0, 0, pl.row_a.size() - 1, 0});
+        anchors.back().jend = rec_of(b);  // rows ascend in b: the last one is the farthest
+        anchors.back().r1 = pl.row_a.size();
+      }
+      pl.row_of[ord[p]] = pl.row_a.size() - 1;
+    }
+    pl.row_off[i + 1] = pl.row_a.size();
+    // a slot is free for an anchor at record ja when its holder's last record is at most ja: at a record the
+    // carried-in anchors are evaluated and freed before new ones start, and head-only anchors end in turn
+    busy.clear();
+    ends.clear();
+    int rounds = 0;
+    for (Anchor &an : anchors) {
+      ends.erase(std::remove_if(ends.begin(), ends.end(), [&](int e) { return e <= an.ja; }), ends.end());
+      ends.push_back(an.jend);
+      pl.need = std::max(pl.need, (int)ends.size());
+      bool placed = false;
+      for (size_t r = 0; !placed; ++r) {
+        if (r == busy.size()) busy.push_back(std::vector<int>((size_t)ns, 0));
+        for (int sl = 0; sl < ns && !placed; ++sl)
+          if (busy[r][sl] <= an.ja) {
+            busy[r][sl] = an.jend;
+            an.round = (int)r;
+            an.slot = sl;
+            placed = true;
+          }
+      }
+      rounds = std::max(rounds, an.round + 1);
+    }
+    pl.rounds = std::max(pl.rounds, rounds);
+    for (int r = 0; r < rounds; ++r) {
+      evs.clear();
+      for (const Anchor &an : anchors) {
+        if (an.round != r) continue;
+        evs.push_back({an.ja, 1, an.a, 0, 0, {an.ja, PAIR_EV_ANCHOR | an.slot << 2, an.a, -1}});
+        for (size_t w = an.r0; w < an.r1; ++w) {
+          const int b = pl.row_b[w], jb = rec_of(b);
+          const PairEvent e{jb, PAIR_EV_EVAL | an.slot << 2, b, (int32_t)(w - row0)};
+          if (jb == an.ja) evs.push_back({jb, 1, an.a, 1, b, e});  // both inside the head
+          else evs.push_back({jb, 0, 0, 0, b, e});
+        }
+        const PairEvent f{an.jend, PAIR_EV_FREE | an.slot << 2, an.a, -1};
+        if (an.jend == an.ja) evs.push_back({an.jend, 1, an.a, 2, 0, f});
+        else evs.push_back({an.jend, 0, 0, 1, an.a, f});
+      }
+      std::sort(evs.begin(), evs.end(), [](const Keyed &x, const Keyed &y) {
+        return std::tie(x.rec, x.phase, x.a, x.kind, x.b, x.ev.op) < std::tie(y.rec, y.phase, y.a, y.kind, y.b, y.ev.op);
+      });
+      for (const Keyed &k : evs) pl.ev.push_back(k.ev);
+    }
+    pl.ev_off[i + 1] = pl.ev.size();
+  }
+  return HMC_OK;
+}
+
+int Ctx::pair_posteriors(int64_t nq, const int32_t *indiv, const int32_t *locus_a, const int32_t *locus_b, int32_t *status,
+                         double *post) {
+  if (!have_estep) return fail(HMC_EARG, "pair posteriors need an E-step first (hmc_resolve_all)");
+  if (estep_gen != model_gen)
+    return fail(HMC_EARG, "pair posteriors: the model changed since the last E-step (hmc_resolve_all again)");
+  if (pan.amax > 44) return fail(HMC_EUNSUPPORTED, "pair posteriors with more than 44 alleles per locus");
+  if (nq < 0 || (nq > 0 && (!indiv || !locus_a || !locus_b))) return fail(HMC_EARG, "pair posteriors: no queries given");
+  pr_ms_struct = pr_ms_fb = pr_ms_sweep = 0;
+  pr_groups = pr_pruned = pr_spilled = pr_ns = pr_rounds = 0;
+  if (nq == 0) return HMC_OK;
+  const int n = nloc();
+  PairPlan pl;
+  int rc;
+  // NS: as asked, else the smallest instantiated that holds every individual's anchors in one round (8 at most)
+  int NS = pr_slots;
+  if (NS == 0) {
+    if ((rc = pair_plan(nq, indiv, locus_a, locus_b, PAIR_SLOTS_MAX, pl))) return rc;
+    NS = pl.need <= 1 ? 1 : pl.need <= 2 ? 2 : pl.need <= 4 ? 4 : 8;
+  }
+  if (NS != PAIR_SLOTS_MAX || pr_slots) {
+    if ((rc = pair_plan(nq, indiv, locus_a, locus_b, NS, pl))) return rc;
+  }
+  pr_ns = pr_ns_run = NS;
+  pr_rounds = pl.rounds;
+  const size_t nr = pl.row_a.size(), ne = pl.ev.size();
+  hipError_t er;
+  if ((er = d_site_off.ensure((size_t)n + 1)) || (er = d_pr_evoff.ensure((size_t)n + 1)) || (er = d_pr_ev.ensure(ne)) ||
+      (er = d_site_status.ensure(nr)) || (er = d_site_post.ensure(nr * 2)) || (er = d_xstatus.ensure(n)) ||
+      (er = d_xre.ensure(n)) || (er = d_xfmax.ensure(n)) ||
+      (er = hipMemcpyAsync(d_site_off.p, pl.row_off.data(), ((size_t)n + 1) * 8, hipMemcpyHostToDevice, st)) ||
+      (er = hipMemcpyAsync(d_pr_evoff.p, pl.ev_off.data(), ((size_t)n + 1) * 8, hipMemcpyHostToDevice, st)) ||
+      (er = hipMemcpyAsync(d_pr_ev.p, pl.ev.data(), ne * sizeof(PairEvent), hipMemcpyHostToDevice, st)) ||
+      (er = hipMemsetAsync(d_site_post.p, 0, nr * 2 * 8, st)) || (er = hipMemsetAsync(d_site_status.p, 0, nr * 4, st)))
+    return hipfail(er, "pair posteriors");
+  // the pass counts in the genotype posteriors' fields: theirs are put back
+  const double g_struct = xp_ms_struct, g_fb = xp_ms_fb, g_sites = xp_ms_sites;
+  const int g_groups = xp_groups, g_pruned = xp_pruned;
+  rc = xp_pass(XP_PAIR, "pair posteriors");
+  pr_ms_struct = xp_ms_struct;
+  pr_ms_fb = xp_ms_fb;
+  pr_ms_sweep = xp_ms_sites;
+  pr_groups = xp_groups;
+  pr_pruned = xp_pruned;
+  xp_ms_struct = g_struct;
+  xp_ms_fb = g_fb;
+  xp_ms_sites = g_sites;
+  xp_groups = g_groups;
+  xp_pruned = g_pruned;
+  if (rc) return rc;
+  std::vector<int32_t> rst(nr);
+  std::vector<double> rpost(nr * 2);
+  if ((er = hipMemcpyAsync(rst.data(), d_site_status.p, nr * 4, hipMemcpyDeviceToHost, st)) ||
+      (er = hipMemcpyAsync(rpost.data(), d_site_post.p, nr * 2 * 8, hipMemcpyDeviceToHost, st)) || (er = sync_st()))
+    return hipfail(er, "pair posteriors");
+  for (int64_t q = 0; q < nq; ++q) {  // rows in the caller's order
+    const size_t r = pl.row_of[(size_t)q];
+    if (status) status[q] = rst[r];
+    if (post) {
+      post[2 * q] = rpost[2 * r];
+      post[2 * q + 1] = rpost[2 * r + 1];
+    }
+  }
+  return HMC_OK;
+}
+
 int Ctx::site_group(const ExactArgs &x, int k, int dev_cu) {
   SiteArgs s;
   s.site_off = d_site_off.p;
@@ -416,6 +643,7 @@ int Ctx::xp_pass(XpMode mode, const char *what) {
     xc_groups = 0;
     xp_ms_fb = xp_ms_sites = 0;
     if (mode == XP_SWITCH) sw_spilled = 0;
+    if (mode == XP_PAIR) pr_spilled = 0;
     rc = estep_split(order, true);
     if (rc != ESTEP_RESTART) break;
   }

@@ -1212,4 +1212,188 @@ hipError_t launch_exact_switch_posteriors(const ExactArgs &a, const SwitchArgs &
   return hipGetLastError();
 }
 
+// Pair posteriors (hmc_pair_posteriors): cis and trans as in
+// exact_switch_posteriors, for pairs (a, b) of heterozygous loci any distance
+// apart, with several anchors live in one labelled forward sweep.  A state t
+// carries 2 NS doubles g[slot][0..1][t]; a slot holds one anchor locus from
+// its record to the record of the farthest b asked for it.  The three steps
+// are the switch kernel's, per slot:
+//   anchor    slot s at record a + 1 from fwd: g[s][o(t)][t] = fwd[t], the
+//             other label 0;
+//   propagate record j from j - 1: a state's contribution words and tpv[t]
+//             are read once, and every live slot takes the switch kernel's two
+//             running sums in the record's contribution order (the first term
+//             assigns, later ones add); dead slots are neither read nor
+//             written;
+//   evaluate  query (a, b) at record b + 1 from a's slot: wavefront 0 owns
+//             cis, wavefront 1 trans, lane l adds states l, l + 64, ...
+//             ascending, the fixed butterfly, one division by the scaled
+//             P(genotype).
+// The host turns an individual's queries into an event list in execution
+// order (PairEvent, exact.hpp): the kernel never searches the queries.  Between
+// events it propagates up to the next event's record while a slot is live and
+// jumps there when none is, which is also how a later round (the anchors that
+// found no free slot among NS) starts again from an earlier record.
+// A query's two doubles are a function of the records, the forward and
+// backward values and (a, b) alone: the slot only names where the anchor's
+// labelled values are kept, so NS, slot, round, the other queries, block size,
+// grid, grouping, shard and tier do not change the bits, and a query whose b
+// is the next heterozygous locus after a repeats exact_switch_posteriors'
+// operations for that site.  No floating-point atomics, no cross-wave sums.
+// The frontiers (32 NS bytes per state for the two) live in LDS when the
+// individual's largest record has at most `tier` states, else in the block's
+// slice of an HBM scratch.
+template <int NS>
+__global__ __launch_bounds__(256) void exact_pair_posteriors(ExactArgs a, PairArgs s) {
+  extern __shared__ __attribute__((aligned(16))) double pr_lds[];  // [2 frontiers][lds_states][NS slots][2 labels]
+  __shared__ int fmx;
+  const int tid = threadIdx.x, NT = blockDim.x;
+  const int lane = tid & (WAVE - 1), wave = tid / WAVE, nw = NT / WAVE;
+  const int L = a.L, hl = a.head_len;
+  for (int q = blockIdx.x; q < a.n_order; q += gridDim.x) {
+    const int bi = a.order[q];
+    const unsigned long long s0 = s.row_off[bi], s1 = s.row_off[bi + 1];
+    if (s0 == s1) continue;
+    const int st0 = a.status[bi];
+    const double pg = a.gprob[bi];
+    const bool resolved = (st0 == EST_OK || st0 == EST_OK_PRUNED) && pg > 0.0 && !isinf(pg);
+    const unsigned long long *roff = a.rec_off + (size_t)bi * (L + 1);
+    const unsigned long long *xo = a.x_off + (size_t)bi * (L + 1);
+    // the individual's largest record (block-uniform after the barrier)
+    int fbig = 0;
+    if (resolved) {
+      __syncthreads();  // every thread has read the previous individual's maximum
+      if (tid == 0) fmx = 0;
+      __syncthreads();
+      int f = 0;
+      for (int j = hl + tid; j <= L; j += NT) f = max(f, (int)a.rec[roff[j]]);
+      atomicMax(&fmx, f);
+      __syncthreads();
+      fbig = fmx;
+    }
+    const bool in_lds = fbig <= s.tier && fbig <= s.lds_states;
+    // (a frontier neither store holds cannot occur: the host sizes the scratch from the group's fmax)
+    const bool fits = in_lds || (s.scratch && fbig <= s.scratch_states);
+    if (!resolved || pg < SITE_PG_MIN || !fits) {  // rows of zeros: unresolved (1), or P(genotype) subnormal (2)
+      for (unsigned long long i = s0 * 2 + tid; i < s1 * 2; i += NT) s.post[i] = 0.0;
+      for (unsigned long long i = s0 + tid; i < s1; i += NT) s.row_status[i] = resolved && fits ? 2 : 1;
+      continue;
+    }
+    const size_t cap = in_lds ? (size_t)s.lds_states : (size_t)s.scratch_states;
+    double *cur = in_lds ? pr_lds : s.scratch + (size_t)blockIdx.x * 4 * NS * cap;
+    double *prev = cur + 2 * NS * cap;
+    const int sc = -ilogb(pg), sa = sc / 2, sb = sc - sa;
+    const double pgs = ldexp(pg, sc);
+    // o(t): the side of state t of record j that carries the lower allele of locus k
+    // (k < head_len: j is the head record; its hdr word carries locus 0 when head_len is 1)
+    auto low_side = [&](const RecView &R, int k, int t) -> int {
+      uint32_t xa, xb;
+      if (k < hl && hl > 1) {
+        const uint32_t *plo = R.cb + R.F + 1, *phi = plo + R.F;
+        xa = a.head_al[(size_t)plo[t] * hl + k];
+        xb = a.head_al[(size_t)phi[t] * hl + k];
+      } else {
+        const uint32_t h = R.hdr[t];
+        xa = h & 0xFFu;
+        xb = (h >> 8) & 0xFFu;
+      }
+      return xa < xb ? 0 : 1;
+    };
+    __syncthreads();  // the previous individual's last readers of the frontiers are done
+    const unsigned long long e0 = s.ev_off[bi], e1 = s.ev_off[bi + 1];
+    unsigned live = 0;     // slots that hold an anchor (block-uniform, as everything the events decide)
+    int j = hl;            // the record `cur` belongs to
+    bool unread = false;   // evaluations since the last barrier may still be reading `cur`
+    for (unsigned long long e = e0; e < e1; ++e) {
+      const PairEvent ev = s.ev[e];
+      const int kind = ev.op & 3, slot = ev.op >> 2;
+      if (ev.rec < hl || ev.rec > L || slot >= NS) continue;  // (the host builds none such)
+      if (live == 0u || ev.rec < j) {  // nothing to carry: the next round, or a gap between intervals
+        j = ev.rec;
+        live = 0u;
+      }
+      while (j < ev.rec) {  // record j + 1 from record j (j + 1 > head_len: never the head record)
+        ++j;
+        double *x = prev;
+        prev = cur;
+        cur = x;
+        const RecView R(a.rec + roff[j], false);
+        for (int t = tid; t < R.F; t += NT) {
+          const double tpv = R.tpv[t];
+          double n0[NS], n1[NS];
+#pragma unroll
+          for (int u = 0; u < NS; ++u) n0[u] = n1[u] = 0.0;
+          const uint32_t r0 = R.cb[t], r1 = R.cb[t + 1];
+          for (uint32_t r = r0; r < r1; ++r) {
+            const uint32_t w = R.ct[r];
+            const bool rv = cw_rev(w);
+            const double2 *p = (const double2 *)(prev + (size_t)cw_state(w) * 2 * NS);
+#pragma unroll
+            for (int u = 0; u < NS; ++u)
+              if ((live >> u) & 1u) {
+                const double2 g = p[u];
+                const double v0 = (rv ? g.y : g.x) * tpv, v1 = (rv ? g.x : g.y) * tpv;
+                n0[u] = r == r0 ? v0 : n0[u] + v0;
+                n1[u] = r == r0 ? v1 : n1[u] + v1;
+              }
+          }
+          double2 *o = (double2 *)(cur + (size_t)t * 2 * NS);
+#pragma unroll
+          for (int u = 0; u < NS; ++u)
+            if ((live >> u) & 1u) o[u] = make_double2(n0[u], n1[u]);
+        }
+        __syncthreads();
+        unread = false;
+      }
+      const RecView R(a.rec + roff[j], j == hl);
+      if (kind == PAIR_EV_EVAL) {
+        if (!((live >> slot) & 1u) || ev.row < 0 || s0 + (unsigned long long)ev.row >= s1) continue;  // (none such)
+        const unsigned long long row = s0 + (unsigned long long)ev.row;
+        const double *bw = (const double *)(a.x + xo[j]) + R.F;
+        for (int w = wave; w < 2; w += nw) {  // wave-uniform: 0 cis, 1 trans
+          double part[1] = {0.0};
+          for (int t = lane; t < R.F; t += WAVE)
+            part[0] += ldexp(cur[((size_t)t * NS + slot) * 2 + (low_side(R, ev.locus, t) ^ w)], sa) * ldexp(bw[t], sb);
+          const double v = group_sum_fixed<WAVE>(part) / pgs;
+          if (lane == 0) s.post[row * 2 + w] = v;
+        }
+        if (tid == 0) s.row_status[row] = 0;
+        unread = true;
+      } else if (kind == PAIR_EV_FREE) {
+        live &= ~(1u << slot);
+      } else if (kind == PAIR_EV_ANCHOR) {
+        if (unread) __syncthreads();  // the sums have read the slot this anchor overwrites
+        const double *fw = (const double *)(a.x + xo[j]);
+        for (int t = tid; t < R.F; t += NT) {
+          const int o = low_side(R, ev.locus, t);
+          double *g = cur + ((size_t)t * NS + slot) * 2;
+          g[o] = fw[t];
+          g[o ^ 1] = 0.0;
+        }
+        __syncthreads();
+        unread = false;
+        live |= 1u << slot;
+      }
+    }
+  }
+}
+
+template <int NS>
+static hipError_t launch_pair(const ExactArgs &a, const PairArgs &s, int grid, hipStream_t st, int block) {
+  hipLaunchKernelGGL(exact_pair_posteriors<NS>, dim3(grid), dim3(block), (size_t)s.lds_states * 32 * NS, st, a, s);
+  return hipGetLastError();
+}
+
+hipError_t launch_exact_pair_posteriors(const ExactArgs &a, const PairArgs &s, int ns, int grid, hipStream_t st, int block) {
+  if (a.n_order <= 0) return hipSuccess;
+  if (block < WAVE || block > 256 || block % WAVE || grid < 1 || !pair_slots_ok(ns) || s.tier < 1 || s.lds_states < 1 ||
+      s.lds_states > pair_tier_max(ns) || !s.row_off || !s.ev_off || !s.ev || !s.post || !s.row_status ||
+      (s.scratch && s.scratch_states < 1))
+    return hipErrorInvalidValue;
+  return ns == 1   ? launch_pair<1>(a, s, grid, st, block)
+         : ns == 2 ? launch_pair<2>(a, s, grid, st, block)
+         : ns == 4 ? launch_pair<4>(a, s, grid, st, block)
+                   : launch_pair<8>(a, s, grid, st, block);
+}
+
 }  // namespace hmc

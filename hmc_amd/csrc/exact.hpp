@@ -123,4 +123,43 @@ constexpr int SWITCH_TIER_MAX = 2032;      // with the kernel's static LDS withi
 // after exact_fb over the same group; block sizes 64, 128, 192 and 256 give the same bits
 hipError_t launch_exact_switch_posteriors(const ExactArgs &a, const SwitchArgs &s, int grid, hipStream_t st, int block = 256);
 
+// Pair posteriors (exact_pair_posteriors): cis / trans for pairs (a, b) of
+// heterozygous loci any distance apart.  An individual's distinct queries are
+// rows of a CSR over batch indices; its sweep is a host-built event list in
+// the order the kernel executes it: per round (one sweep over the records)
+// ascending record, and at a record the evaluations and frees of the anchors
+// carried in before the anchors that start there (an anchor inside the head is
+// followed at once by its own head evaluations).
+enum : int32_t { PAIR_EV_EVAL = 0, PAIR_EV_FREE = 1, PAIR_EV_ANCHOR = 2 };
+struct PairEvent {
+  int32_t rec;    // the record the event happens at (head_len for loci inside the head)
+  int32_t op;     // kind | slot << 2
+  int32_t locus;  // anchor: locus a; evaluate: locus b
+  int32_t row;    // evaluate: the output row; else -1
+};
+struct PairArgs {
+  const unsigned long long *row_off = nullptr;  // [batch + 1]
+  const unsigned long long *ev_off = nullptr;   // [batch + 1]
+  const PairEvent *ev = nullptr;
+  double *post = nullptr;                        // [rows][2]
+  int32_t *row_status = nullptr;                 // [rows] as SiteArgs::site_status
+  int tier = 0;                                  // an individual whose largest record has at most this many states sweeps in LDS
+  int lds_states = 0;                            // states the launch's LDS holds: min(tier, the group's fmax), 32 NS B each
+  double *scratch = nullptr;                     // [grid][4 NS scratch_states]: the frontiers of individuals past the tier
+  int scratch_states = 0;                        // the group's fmax when scratch is given
+};
+// Slots per state (NS): 1, 2, 4 and 8 are instantiated.  pair_tier_max: the
+// states whose frontiers the 64 KiB a launch gets unasked hold beside the
+// kernel's static LDS.  The default tier is that of the largest NS at every
+// NS (8 / 16 / 32 / 64 KiB of LDS): on cfg 2 the sweep measured faster with it
+// than with the whole 64 KiB at NS = 2 and 4 (6.5 against 7.7 ms, 12.6 against
+// 14.7 ms) — more blocks to a compute unit outweigh the frontiers
+// that move to device memory.
+constexpr int PAIR_SLOTS_MAX = 8;
+constexpr bool pair_slots_ok(int ns) { return ns == 1 || ns == 2 || ns == 4 || ns == 8; }
+constexpr int pair_tier_max(int ns) { return 65024 / (32 * ns); }  // 2032, 1016, 508, 254
+constexpr int PAIR_TIER_DEFAULT = pair_tier_max(PAIR_SLOTS_MAX);
+// after exact_fb over the same group; NS, block sizes 64 .. 256 and the grid do not change the bits
+hipError_t launch_exact_pair_posteriors(const ExactArgs &a, const PairArgs &s, int ns, int grid, hipStream_t st, int block = 256);
+
 }  // namespace hmc

@@ -556,6 +556,53 @@ class HaploModel:
         """switch_posteriors as text, one line per site of status 0 (hmc_write_switch_posteriors)."""
         self._check(lib().hmc_write_switch_posteriors(self._h, path.encode()))
 
+    def pair_span_list(self, span: int) -> dict:
+        """The queries (h_q, h_q+d), 1 <= d <= span, of every individual of
+        this rank's shard, h1 < h2 < ... its heterozygous loci: indiv[n],
+        locus_a[n], locus_b[n], individual-major, then a, then b ascending
+        (hmc_pair_span_list).  Counted from the panel: no model, no device."""
+        n = C.c_int64()
+        self._check(lib().hmc_pair_span_list(self._h, int(span), C.byref(n), None, None, None))
+        out = dict(indiv=np.zeros(n.value, np.int32), locus_a=np.zeros(n.value, np.int32), locus_b=np.zeros(n.value, np.int32))
+        self._check(lib().hmc_pair_span_list(self._h, int(span), C.byref(n), _p(out["indiv"], C.c_int32),
+                                             _p(out["locus_a"], C.c_int32), _p(out["locus_b"], C.c_int32)))
+        return out
+
+    def pair_posteriors(self, indiv, locus_a, locus_b) -> dict:
+        """cis / trans for the given pairs of heterozygous loci, any distance
+        apart, under the model of the last resolve_all (hmc_pair_posteriors).
+        Query q is (indiv[q], locus_a[q] < locus_b[q]); rows come in the
+        caller's order: status[n] (0 ok; rows of zeros: 1 individual
+        unresolved, 2 its P(genotype) subnormal) and post[n][2] = (cis,
+        trans), defined as for switch_posteriors."""
+        qi, qa, qb = (np.ascontiguousarray(x, np.int32).reshape(-1) for x in (indiv, locus_a, locus_b))
+        if not len(qi) == len(qa) == len(qb):
+            raise ValueError("indiv, locus_a and locus_b differ in length")
+        n = len(qi)
+        out = dict(status=np.zeros(n, np.int32), post=np.zeros((n, 2), np.float64))
+        self._check(lib().hmc_pair_posteriors(self._h, n, _p(qi, C.c_int32), _p(qa, C.c_int32), _p(qb, C.c_int32),
+                                              _p(out["status"], C.c_int32), _p(out["post"], C.c_double)))
+        return out
+
+    def pair_stats(self) -> dict:
+        """Device ms and counts of the last pair_posteriors (hmc_last_pair_stats)."""
+        s, f, k = C.c_double(), C.c_double(), C.c_double()
+        g, p, sp, ns, r = C.c_int(), C.c_int(), C.c_int(), C.c_int(), C.c_int()
+        self._check(lib().hmc_last_pair_stats(self._h, C.byref(s), C.byref(f), C.byref(k), C.byref(g), C.byref(p),
+                                              C.byref(sp), C.byref(ns), C.byref(r)))
+        return dict(structure_ms=s.value, fb_ms=f.value, sweep_ms=k.value, groups=g.value, n_pruned=p.value,
+                    n_spilled=sp.value, slots=ns.value, max_rounds=r.value)
+
+    def set_pair_tuning(self, slots: int = 0, tier: int = 0):
+        """Anchors a state carries at once in the pair sweep (1, 2, 4 or 8) and
+        states per locus it keeps in LDS; 0 = automatic for each.  Results do
+        not depend on it."""
+        self._check(lib().hmc_set_pair_tuning(self._h, int(slots), int(tier)))
+
+    def write_pair_posteriors(self, path: str, span: int):
+        """pair_posteriors of pair_span_list(span) as text, one line per query of status 0 (hmc_write_pair_posteriors)."""
+        self._check(lib().hmc_write_pair_posteriors(self._h, path.encode(), int(span)))
+
     def timings(self) -> dict:
         f, t, m = C.c_double(), C.c_double(), C.c_double()
         self._check(lib().hmc_last_timings(self._h, C.byref(f), C.byref(t), C.byref(m)))

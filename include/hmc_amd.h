@@ -312,6 +312,48 @@ int hmc_switch_posteriors(hmc_ctx *ctx, int64_t *n_sites, int32_t *indiv, int32_
  * Replaces no reference interface. */
 int hmc_last_switch_stats(const hmc_ctx *ctx, double *structure_ms, double *fb_ms, double *sweep_ms, int *groups,
                           int *n_pruned, int *n_spilled);
+/* Pair posteriors: cis / trans for any two heterozygous loci of an individual,
+ * any distance apart (compound heterozygotes, phase-confidence matrices).  A
+ * query q is (indiv[q], locus_a[q], locus_b[q]) with locus_a < locus_b, both
+ * heterozygous in the input (both alleles present and different); queries need
+ * not be consecutive, sorted or distinct.  post[q][0] (cis) and post[q][1]
+ * (trans) are defined as for hmc_switch_posteriors, by lower allele-table
+ * index, and are exact sums over the lattice states: the consecutive switch
+ * posteriors cannot be multiplied along the way, because the switches are not
+ * independent under a variable-order chain.  One labelled forward sweep per
+ * individual carries several anchors at once; anchors that overlap more than
+ * the sweep holds take further rounds, so any set of queries works.  Rows come
+ * in the caller's order: status[n], post[n][2] (either may be NULL); status
+ * 0 / 1 / 2 as for hmc_switch_posteriors, rows of status 1 and 2 are zeros.
+ * For a query whose locus_b is the next heterozygous locus after locus_a the
+ * row has the bits hmc_switch_posteriors returns for that site.  n = 0 is
+ * HMC_OK with no device work.  HMC_EARG, with a message naming the first
+ * offending query, when an individual is outside this rank's shard, when
+ * locus_a >= locus_b, when a locus is out of range or when a locus is not
+ * heterozygous in the input for that individual; HMC_EARG when no E-step has
+ * run or the model has changed since the last one; HMC_EUNSUPPORTED as for
+ * hmc_genotype_posteriors.  Runs its own forward-backward pass and changes no
+ * later result.  The bits of a row depend on the model and on (indiv,
+ * locus_a, locus_b) alone: not on the other queries of the call, launch
+ * shapes, store budgets, sharding or hmc_set_pair_tuning.
+ * Replaces no reference interface. */
+int hmc_pair_posteriors(hmc_ctx *ctx, int64_t n, const int32_t *indiv, const int32_t *locus_a, const int32_t *locus_b,
+                        int32_t *status, double *post);
+/* The queries (h_q, h_q+d), 1 <= d <= span, of every individual of this
+ * rank's shard, h1 < h2 < ... its heterozygous loci: individual-major, then
+ * locus_a ascending, then locus_b ascending; *n of them.  With indiv, locus_a
+ * and locus_b NULL the call only counts; it needs no model and no device.
+ * span = 1 is the site list of hmc_switch_posteriors.  HMC_EARG for span < 1.
+ * Replaces no reference interface. */
+int hmc_pair_span_list(hmc_ctx *ctx, int span, int64_t *n, int32_t *indiv, int32_t *locus_a, int32_t *locus_b);
+/* Last hmc_pair_posteriors: device ms of its structure passes, of the
+ * forward-backward kernel and of the labelled forward sweep; groups the
+ * individuals ran in; individuals on pruned records; individuals whose largest
+ * frontier exceeded the sweep's LDS tier and went through device memory; the
+ * slots per state (NS) the sweep used; the largest number of rounds any
+ * individual took.  Replaces no reference interface. */
+int hmc_last_pair_stats(const hmc_ctx *ctx, double *structure_ms, double *fb_ms, double *sweep_ms, int *groups, int *n_pruned,
+                        int *n_spilled, int *slots, int *max_rounds);
 /* ---- whole EM: HaploModel::run (HaploModel.cpp:117-155) ------------------ */
 typedef struct hmc_iter_log {
   double log_likelihood;
@@ -410,6 +452,14 @@ int hmc_write_posteriors(hmc_ctx *ctx, const char *path);
  * same doubles).  Needs a preceding hmc_resolve_all or hmc_run.
  * Replaces no reference interface. */
 int hmc_write_switch_posteriors(hmc_ctx *ctx, const char *path);
+/* hmc_pair_posteriors of hmc_pair_span_list(span) as text (hmc_resolve
+ * --output-pair-posteriors FILE --pair-span K): the header
+ * "Id\tMarkerA\tMarkerB\tAlleleA\tAlleleB\tCis\tTrans", then one line per query
+ * of status 0 in the list's order, spelled as hmc_write_switch_posteriors
+ * spells a site (%.17g: the numbers read back to the same doubles).  Needs a
+ * preceding hmc_resolve_all or hmc_run; HMC_EARG for span < 1.
+ * Replaces no reference interface. */
+int hmc_write_pair_posteriors(hmc_ctx *ctx, const char *path, int span);
 /* ---- tuning -------------------------------------------------------------- */
 /* frontier_cap: initial states per locus and individual (doubles on
  * overflow, at most 2 097 151); trace_bytes: trace-store budget (0 =
@@ -446,6 +496,17 @@ int hmc_set_store_budgets(hmc_ctx *ctx, uint64_t trace_bytes, uint64_t record_by
  * depend on it (it lets small panels take the device-memory path).
  * Replaces no reference interface. */
 int hmc_set_switch_tier(hmc_ctx *ctx, int states);
+/* Schedule of hmc_pair_posteriors, 0 = automatic for each.  slots: anchors a
+ * state carries at once (NS: 1, 2, 4 or 8; automatic: the smallest that holds
+ * every individual's overlapping anchors in one round, 8 at most).  tier_states:
+ * states per locus whose frontiers the sweep keeps in LDS (32 NS bytes per
+ * state; automatic: 254 at every NS, measured faster than the whole 64 KiB at
+ * the smaller NS); an individual with a larger frontier goes through a
+ * device-memory scratch.  HMC_EARG for a slot count that is not instantiated
+ * or a tier above 254, what the LDS holds at the largest NS.  Results do not
+ * depend on it.
+ * Replaces no reference interface. */
+int hmc_set_pair_tuning(hmc_ctx *ctx, int slots, int tier_states);
 /* E-step implementation: 0 (default) = two passes, a structure pass that
  * replays extendAll/addHaploPair (HaploBuilder.cpp:226-261) on pattern ids
  * and a value pass with the k-best lists; individuals whose forward

@@ -15,6 +15,9 @@ struct Options {
   std::string model = "MV", format = "PHASE";
   int mc_order = 1, num_patterns = -1;
   bool exact = false, output_patterns = false, output_posteriors = false, output_switch_posteriors = false;
+  std::string output_pair_posteriors;  // --output-pair-posteriors FILE
+  int pair_span = 0;                   // --pair-span K (required with it, >= 1)
+  bool have_pair_span = false;
 };
 
 // --output-posteriors (no reference counterpart): <first file>.posteriors, the
@@ -40,7 +43,9 @@ constexpr const char *USAGE =
     "                        final model (the model of the last E-step of the run)\n"
     "  --output-switch-posteriors  write <datafile>.switches: for every pair of consecutive heterozygous\n"
     "                        loci of an individual, the probability that their lower alleles share a\n"
-    "                        haplotype (cis) and that they do not (trans), under the final model";
+    "                        haplotype (cis) and that they do not (trans), under the final model\n"
+    "  --output-pair-posteriors FILE --pair-span K  write FILE: cis and trans for every pair of an\n"
+    "                        individual's heterozygous loci at most K heterozygous loci apart (K >= 1)";
 
 // 0 on success; otherwise `err` says what is wrong (a missing value, an
 // unknown option, no data file).
@@ -69,6 +74,8 @@ inline int parse_options(int argc, const char *const *argv, Options &o, std::str
     else if (a == "--output-patterns") { if (!next()) return 1; o.output_patterns = true; }  // HMC.cpp:30, 229-232
     else if (a == "--output-posteriors") o.output_posteriors = true;
     else if (a == "--output-switch-posteriors") o.output_switch_posteriors = true;
+    else if (a == "--output-pair-posteriors") { if (!next()) return 1; o.output_pair_posteriors = v; }
+    else if (a == "--pair-span") { if (!next()) return 1; o.pair_span = atoi(v); o.have_pair_span = true; }
     else if (a == "-m" || a == "--model") { if (!next()) return 1; o.model = v; }          // HMC.cpp:35
     else if (a == "-o" || a == "--mc-order") { if (!next()) return 1; o.mc_order = atoi(v); }      // HMC.cpp:41
     else if (a == "-n" || a == "--num-patterns") { if (!next()) return 1; o.num_patterns = atoi(v); }  // HMC.cpp:38
@@ -77,6 +84,14 @@ inline int parse_options(int argc, const char *const *argv, Options &o, std::str
   }
   if (o.files.empty()) {
     err = USAGE;
+    return 1;
+  }
+  if (!o.output_pair_posteriors.empty() && (!o.have_pair_span || o.pair_span < 1)) {
+    err = "--output-pair-posteriors needs --pair-span K with K >= 1\n" + std::string(USAGE);
+    return 1;
+  }
+  if (o.have_pair_span && o.output_pair_posteriors.empty()) {
+    err = "--pair-span needs --output-pair-posteriors FILE\n" + std::string(USAGE);
     return 1;
   }
   return 0;

@@ -11,12 +11,15 @@
 //               [-m MV|MC|MA] [-o mc_order] [--exact-estimate] [-i 1]
 //               [--sample-size 10] [--min-pattern-len 1] [--max-pattern-len 30]
 //               [--output-patterns x] [--output-posteriors] [--output-switch-posteriors]
-//               [--device 0] datafile ...
+//               [--output-pair-posteriors FILE --pair-span K] [--device 0] datafile ...
 // --output-posteriors (no reference counterpart) writes <first file>.posteriors:
 // genotype posteriors at the loci with a missing input allele, under the final
 // model (hmc_write_posteriors).  --output-switch-posteriors (none either)
 // writes <first file>.switches: cis and trans posteriors between consecutive
 // heterozygous loci under the same model (hmc_write_switch_posteriors).
+// --output-pair-posteriors FILE --pair-span K (none either) writes FILE: cis
+// and trans for every pair of an individual's heterozygous loci at most K
+// heterozygous loci apart (hmc_write_pair_posteriors).
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -90,6 +93,9 @@ int main(int argc, char **argv) {
   if (o.output_switch_posteriors) {  // of the same E-step
     const std::string sf = files[0] + ".switches";
     if ((rc = hmc_write_switch_posteriors(ctx, sf.c_str()))) die("hmc_write_switch_posteriors");
+  }
+  if (!o.output_pair_posteriors.empty()) {  // of the same E-step
+    if ((rc = hmc_write_pair_posteriors(ctx, o.output_pair_posteriors.c_str(), o.pair_span))) die("hmc_write_pair_posteriors");
   }
   hmc_ctx_destroy(ctx);
   return 0;
