@@ -90,6 +90,11 @@ _SIGS = [
     ("hmc_pair_span_list", _i, [_vp, _i, _P(C.c_int64), _P(C.c_int32), _P(C.c_int32), _P(C.c_int32)]),
     ("hmc_last_pair_stats", _i, [_vp, _P(_d), _P(_d), _P(_d), _P(_i), _P(_i), _P(_i), _P(_i), _P(_i)]),
     ("hmc_set_pair_tuning", _i, [_vp, _i, _i]),
+    ("hmc_posterior_draws", _i, [_vp, C.c_int64, _P(C.c_int32), _i, _u64, _P(C.c_int32), _P(_d), _P(C.c_int32)]),
+    ("hmc_last_draw_stats", _i, [_vp, _P(_d), _P(_d), _P(_d), _P(_i), _P(_i)]),
+    ("hmc_set_draw_tuning", _i, [_vp, _i, _i]),
+    ("hmc_write_posterior_draws", _i, [_vp, _cp, _i, _u64]),
+    ("hmc_test_draw_uniform", _d, [_u64, C.c_int32, C.c_int32, C.c_int32]),
     ("hmc_clear_samples", _i, [_vp]),
     ("hmc_run", _i, [_vp, _i, _P(IterLog), _i, _P(_i), _P(_d), _P(_u64), _P(_i)]),
     ("hmc_em_iteration", _i, [_vp, _i, _i, _i, _P(_d), _P(IterLog), _P(_i)]),

@@ -9,6 +9,7 @@
 //   HaploModel::resolveAll        HaploModel.cpp:79-115      -> Ctx::estep (estep.hip)
 //   HaploModel::run               HaploModel.cpp:117-155     -> Ctx::run
 #include "ctx.hpp"
+#include "philox.hpp"
 
 
 using hmc::Ctx;
@@ -987,6 +988,42 @@ int hmc_set_pair_tuning(hmc_ctx *h, int slots, int tier_states) {
   return HMC_OK;
 }
 
+int hmc_posterior_draws(hmc_ctx *h, int64_t n, const int32_t *indiv, int draws, uint64_t seed, int32_t *hap, double *prob,
+                        int32_t *status) {
+  if (!h) return HMC_EARG;
+  Ctx &c = h->c;
+  if (!c.have_panel) return c.fail(HMC_EARG, "no panel loaded");
+  return c.posterior_draws(n, indiv, draws, seed, hap, prob, status);
+}
+
+int hmc_last_draw_stats(const hmc_ctx *h, double *structure_ms, double *fb_ms, double *draw_ms, int *groups, int *n_pruned) {
+  if (!h) return HMC_EARG;
+  if (structure_ms) *structure_ms = h->c.dr_ms_struct;
+  if (fb_ms) *fb_ms = h->c.dr_ms_fb;
+  if (draw_ms) *draw_ms = h->c.dr_ms_draw;
+  if (groups) *groups = h->c.dr_groups;
+  if (n_pruned) *n_pruned = h->c.dr_pruned;
+  return HMC_OK;
+}
+
+// Test seam of hmc_posterior_draws (not in the public header; results do not
+// depend on it): lds_chunks = final records of at most this many chunks of 64
+// states keep their prefix sums in LDS (-1 the default and the most, 1 024; 0
+// sends every record through the device scratch that larger ones always take);
+// forward_only = 0 runs exact_fb's backward half as well.
+int hmc_set_draw_tuning(hmc_ctx *h, int lds_chunks, int forward_only) {
+  if (!h) return HMC_EARG;
+  if (lds_chunks < -1 || lds_chunks > hmc::DRAW_LDS_CHUNKS)
+    return h->c.fail(HMC_EARG, "draw tuning: %d chunks are outside [-1, %d]", lds_chunks, hmc::DRAW_LDS_CHUNKS);
+  h->c.dr_lds_chunks = lds_chunks;
+  h->c.dr_forward_only = forward_only != 0;
+  return HMC_OK;
+}
+
+double hmc_test_draw_uniform(uint64_t seed, int32_t indiv, int32_t draw, int32_t step) {
+  return hmc::draw_uniform(seed, (uint32_t)indiv, (uint32_t)draw, (uint32_t)step);
+}
+
 int hmc_run(hmc_ctx *h, int max_iteration, hmc_iter_log *log, int log_cap, int *iterations, double *t_m0_s,
             uint64_t *r_m0, int *n_patterns0) {
   if (!h) return HMC_EARG;
@@ -1156,6 +1193,54 @@ int hmc_write_pair_posteriors(hmc_ctx *h, const char *path, int span) {
     put_lower(indiv[q], la[q]);
     put_lower(indiv[q], lb[q]);
     fprintf(fp, "\t%.17g\t%.17g\n", post[2 * q], post[2 * q + 1]);
+  }
+  const bool bad = ferror(fp) != 0;
+  if (fclose(fp) != 0 || bad) return c.fail(HMC_EIO, "Can not write file %s!", path);
+  return HMC_OK;
+}
+
+int hmc_write_posterior_draws(hmc_ctx *h, const char *path, int draws, uint64_t seed) {
+  if (!h || !path || !h->c.have_panel) return HMC_EARG;
+  Ctx &c = h->c;
+  if (draws < 1) return c.fail(HMC_EARG, "posterior draws: draws = %d is below 1", draws);
+  const int n = c.nloc(), L = c.pan.L;
+  // individuals in batches whose haplotypes take at most 256 MiB of host memory; a draw does not
+  // depend on the other individuals of its call, so the lines are those of one call for the shard
+  const size_t per = (size_t)draws * 2 * L;
+  const int nb = (int)std::max<size_t>(1, std::min<size_t>((size_t)std::max(n, 1), ((size_t)64 << 20) / per));
+  std::vector<int32_t> hap((size_t)nb * per), status(nb), indiv(nb);
+  std::vector<double> prob((size_t)nb * draws);
+  FILE *fp = nullptr;
+  hmc::FileData d;
+  for (int b0 = 0; b0 < n || !fp; b0 += nb) {
+    const int k = std::max(0, std::min(nb, n - b0));
+    for (int i = 0; i < k; ++i) indiv[i] = c.i0 + b0 + i;
+    int rc;
+    // (the first batch before the file is opened: a call that fails leaves no file behind)
+    if ((rc = c.posterior_draws(k, indiv.data(), draws, seed, hap.data(), prob.data(), status.data()))) {
+      if (fp) fclose(fp);
+      return rc;
+    }
+    if (!fp) {
+      if (!(fp = fopen(path, "w"))) return c.fail(HMC_EIO, "Can not open file %s!", path);
+      d = writer_meta(c);
+      fprintf(fp, "Id\tDraw\tPosterior\tHaplotype0\tHaplotype1\n");
+    }
+    for (int i = 0; i < k; ++i) {
+      if (status[i] != 0) continue;
+      for (int q = 0; q < draws; ++q) {
+        fprintf(fp, "%s\t%d\t%.17g", d.ids[indiv[i]].c_str(), q, prob[(size_t)i * draws + q]);
+        for (int side = 0; side < 2; ++side) {
+          const int32_t *row = hap.data() + (((size_t)i * draws + q) * 2 + side) * L;
+          for (int l = 0; l < L; ++l) {  // as the genotype files spell alleles: characters ('S') or integers ('M')
+            fputc(l ? ' ' : '\t', fp);
+            if (c.pan.types[l] == 'S') fputc((char)row[l], fp);
+            else fprintf(fp, "%d", row[l]);
+          }
+        }
+        fputc('\n', fp);
+      }
+    }
   }
   const bool bad = ferror(fp) != 0;
   if (fclose(fp) != 0 || bad) return c.fail(HMC_EIO, "Can not write file %s!", path);

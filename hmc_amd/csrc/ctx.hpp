@@ -809,12 +809,13 @@ struct Ctx {
   void site_list(SiteList &sl) const;
   int site_group(const ExactArgs &x, int k, int dev_cu);
   // what the exact group runs after exact_fb in place of the trie walk
-  enum XpMode { XP_OFF = 0, XP_GENOTYPE = 1, XP_SWITCH = 2, XP_PAIR = 3 };
+  enum XpMode { XP_OFF = 0, XP_GENOTYPE = 1, XP_SWITCH = 2, XP_PAIR = 3, XP_DRAW = 4 };
   XpMode xp_mode = XP_OFF;
   // The part the two posterior calls share: every individual of the shard
   // through estep_split(order, true) with xp_mode = mode, and whatever that
   // pass shares with the E-step saved before and put back after.
-  int xp_pass(XpMode mode, const char *what);
+  // (only: the individuals of the shard that take part; the others are not touched)
+  int xp_pass(XpMode mode, const char *what, const std::vector<char> *only = nullptr);
   // Switch posteriors (hmc_switch_posteriors): sites are an individual's pairs
   // of consecutive heterozygous loci, individual-major, locus_a ascending;
   // exact_switch_posteriors per group (XP_SWITCH).
@@ -862,6 +863,34 @@ struct Ctx {
   // of the last call, as sw_* above; pr_ns: the NS used, pr_rounds: most rounds of any individual
   double pr_ms_struct = 0, pr_ms_fb = 0, pr_ms_sweep = 0;
   int pr_groups = 0, pr_pruned = 0, pr_spilled = 0, pr_ns = 0, pr_rounds = 0;
+  // Posterior draws (hmc_posterior_draws): `draws` haplotype pairs per asked
+  // individual, sampled backwards through exact_fb's forward values;
+  // exact_posterior_draws per group (XP_DRAW), in batches whose device output
+  // stays within DRAW_OUT_BYTES.  Rows are the caller's: an individual asked
+  // for twice is drawn once and copied to both rows.
+  int posterior_draws(int64_t n, const int32_t *indiv, int draws, uint64_t seed, int32_t *hap, double *prob, int32_t *status);
+  int draw_group(const ExactArgs &x, const int32_t *ids, int k, int dev_cu);
+  static constexpr size_t DRAW_OUT_BYTES = (size_t)512 << 20;
+  struct DrawCall {  // the running call
+    int draws = 0;
+    uint64_t seed = 0;
+    int32_t *hap = nullptr;
+    double *prob = nullptr;
+    std::vector<int64_t> row_off, rows;  // CSR over the shard's individuals: the caller's rows that ask for each
+    std::vector<int32_t> status;         // [shard] 1 until the individual's group has run
+  } dr;
+  DevBuf<int32_t> d_dr_order, d_dr_status, d_dr_hap, d_dr_sym;  // (hap, sym: the transposing kernel's)
+  DevBuf<uint8_t> d_dr_al;
+  DevBuf<double> d_dr_prob, d_dr_csum;
+  // hmc_set_draw_tuning (test seam, not in the public header): the final
+  // record's prefix sums in LDS up to this many chunks of 64 states (-1:
+  // DRAW_LDS_CHUNKS; larger records take the device scratch anyway); whether
+  // exact_fb skips its backward half
+  int dr_lds_chunks = -1;
+  bool dr_forward_only = true;  // exact_fb without its backward half for this call (hmc_set_draw_tuning)
+  // of the last call, as sw_* above; dr_ms_draw: exact_posterior_draws and draws_to_symbols
+  double dr_ms_struct = 0, dr_ms_fb = 0, dr_ms_draw = 0;
+  int dr_groups = 0, dr_pruned = 0;
   DevBuf<unsigned long long> d_site_off;
   DevBuf<int32_t> d_site_locus, d_site_status;
   DevBuf<double> d_site_post;

@@ -200,6 +200,7 @@ int Ctx::exact_group(const int32_t *ids, int k, const std::function<int(std::vec
   x.head_al = d_head_al.p;
   x.acc_freq = d_xacc.p;
   x.acc_prefix = d_xacc.p + xacc_nc;
+  x.forward_only = xp_mode == XP_DRAW && dr_forward_only;
   if (xc_reuse) {  // a later round over the same group: records and fwd/bwd sums are still in place
     x.fmax = xc_fmax;
     return exact_walk_group(x, k, dev_cu);
@@ -252,6 +253,7 @@ int Ctx::exact_group(const int32_t *ids, int k, const std::function<int(std::vec
   if (xp_mode == XP_GENOTYPE) return site_group(x, k, dev_cu);  // genotype posteriors: no trie, no walk
   if (xp_mode == XP_SWITCH) return switch_group(x, ids, fm, k, dev_cu);
   if (xp_mode == XP_PAIR) return pair_group(x, ids, fm, k, dev_cu);
+  if (xp_mode == XP_DRAW) return draw_group(x, ids, k, dev_cu);
   return exact_walk_group(x, k, dev_cu);
 }
 
@@ -580,6 +582,156 @@ int Ctx::pair_posteriors(int64_t nq, const int32_t *indiv, const int32_t *locus_
   return HMC_OK;
 }
 
+int Ctx::draw_group(const ExactArgs &x, const int32_t *ids, int k, int dev_cu) {
+  const int L = pan.L, D = dr.draws, A = pan.amax;
+  std::vector<int32_t> sel;  // the group's individuals that the caller asked for
+  for (int q = 0; q < k; ++q)
+    if (dr.row_off[ids[q] + 1] > dr.row_off[ids[q]]) sel.push_back(ids[q]);
+  if (sel.empty()) return HMC_OK;
+  const size_t per = (size_t)2 * L * D;   // haplotype entries of one individual
+  // device output of one individual: prob, the draw-minor bytes and the symbols
+  const size_t dev_bytes = (size_t)D * 8 + (dr.hap ? per * 5 : 0);
+  const size_t cap = std::max<size_t>(1, DRAW_OUT_BYTES / dev_bytes);
+  const int ndc = (D + DRAW_BLOCK - 1) / DRAW_BLOCK;
+  const int nchunks = (std::max(x.fmax, 1) + WAVE - 1) / WAVE;
+  const int lds_chunks = dr_lds_chunks < 0 ? DRAW_LDS_CHUNKS : std::min(dr_lds_chunks, DRAW_LDS_CHUNKS);
+  hipError_t e;
+  std::vector<int32_t> symtab((size_t)L * A, -1);  // the panel's symbol table, [locus][allele index]
+  for (int l = 0; l < L; ++l)
+    for (size_t j = 0; j < pan.sym[l].size(); ++j) symtab[(size_t)l * A + j] = pan.sym[l][j].first;
+  if (dr.hap &&
+      ((e = d_dr_sym.ensure(symtab.size())) ||
+       (e = hipMemcpyAsync(d_dr_sym.p, symtab.data(), symtab.size() * 4, hipMemcpyHostToDevice, st)) || (e = sync_st())))
+    return hipfail(e, "exact_posterior_draws");
+  std::vector<int32_t> h_st;
+  std::vector<double> h_prob;
+  for (size_t pos = 0; pos < sel.size(); pos += cap) {
+    const int nb = (int)std::min(cap, sel.size() - pos);
+    const int grid = (int)std::max<long long>(1, std::min<long long>((long long)nb * ndc, (long long)dev_cu * 8));
+    ExactArgs xb = x;
+    DrawArgs s;
+    if ((e = d_dr_order.ensure(nb)) || (e = d_dr_status.ensure(nb)) || (e = d_dr_prob.ensure((size_t)nb * D)) ||
+        (dr.hap && (e = d_dr_al.ensure((size_t)nb * per))) || (dr.hap && (e = d_dr_hap.ensure((size_t)nb * per))) ||
+        (nchunks > lds_chunks && (e = d_dr_csum.ensure((size_t)grid * nchunks))) ||
+        (e = hipMemsetAsync(d_dr_status.p, 0, (size_t)nb * 4, st)))  // the kernel writes the non-zero ones
+      return hipfail(e, "exact_posterior_draws");
+    int rc;
+    if ((rc = upload_order(d_dr_order, sel.data() + pos, nb))) return rc;
+    xb.order = d_dr_order.p;
+    xb.n_order = nb;
+    s.draws = D;
+    s.seed = dr.seed;
+    s.indiv0 = i0;
+    s.al = dr.hap ? d_dr_al.p : nullptr;
+    s.prob = d_dr_prob.p;
+    s.status = d_dr_status.p;
+    s.lds_chunks = lds_chunks;
+    if (nchunks > lds_chunks) {
+      s.csum = d_dr_csum.p;
+      s.csum_stride = nchunks;
+    }
+    hipEventRecord(ev[0], st);
+    if ((e = launch_exact_posterior_draws(xb, s, grid, st))) return hipfail(e, "exact_posterior_draws");
+    if (dr.hap && (e = launch_draws_to_symbols(d_dr_al.p, d_dr_sym.p, d_dr_hap.p, nb, L, D, A, st)))
+      return hipfail(e, "draws_to_symbols");
+    hipEventRecord(ev[1], st);
+    h_st.resize(nb);
+    h_prob.resize((size_t)nb * D);
+    if ((e = hipMemcpyAsync(h_st.data(), d_dr_status.p, (size_t)nb * 4, hipMemcpyDeviceToHost, st)) ||
+        (e = hipMemcpyAsync(h_prob.data(), d_dr_prob.p, (size_t)nb * D * 8, hipMemcpyDeviceToHost, st)) ||
+        (e = sync_st()))
+      return hipfail(e, "exact_posterior_draws");
+    float ms = 0;
+    hipEventElapsedTime(&ms, ev[0], ev[1]);
+    xp_ms_sites += ms;
+    if (dr.hap) {  // each individual's symbols straight into the first of the caller's rows that ask for it
+      for (int u = 0; u < nb; ++u)
+        if (h_st[u] == 0 && (e = hipMemcpyAsync(dr.hap + (size_t)dr.rows[dr.row_off[sel[pos + u]]] * per, d_dr_hap.p + (size_t)u * per,
+                                                per * 4, hipMemcpyDeviceToHost, st)))
+          return hipfail(e, "exact_posterior_draws");
+      if ((e = sync_st())) return hipfail(e, "exact_posterior_draws");
+    }
+    for (int u = 0; u < nb; ++u) {
+      const int bi = sel[pos + u];
+      dr.status[bi] = h_st[u];
+      if (h_st[u] != 0) continue;  // (the caller's rows get the input genotype)
+      int32_t *first = dr.hap ? dr.hap + (size_t)dr.rows[dr.row_off[bi]] * per : nullptr;
+      for (int64_t w = dr.row_off[bi]; w < dr.row_off[bi + 1]; ++w) {
+        const int64_t row = dr.rows[w];
+        if (dr.prob) std::copy(h_prob.begin() + (size_t)u * D, h_prob.begin() + (size_t)(u + 1) * D, dr.prob + row * D);
+        if (dr.hap && w > dr.row_off[bi]) std::copy(first, first + per, dr.hap + (size_t)row * per);  // a repeated individual
+      }
+    }
+  }
+  return HMC_OK;
+}
+
+int Ctx::posterior_draws(int64_t n, const int32_t *indiv, int draws, uint64_t seed, int32_t *hap, double *prob, int32_t *status) {
+  if (!have_estep) return fail(HMC_EARG, "posterior draws need an E-step first (hmc_resolve_all)");
+  if (estep_gen != model_gen)
+    return fail(HMC_EARG, "posterior draws: the model changed since the last E-step (hmc_resolve_all again)");
+  if (pan.amax > 44) return fail(HMC_EUNSUPPORTED, "posterior draws with more than 44 alleles per locus");
+  if (draws < 1) return fail(HMC_EARG, "posterior draws: draws = %d is below 1", draws);
+  const int nl = nloc(), L = pan.L;
+  if (!indiv) n = nl;
+  if (n < 0) return fail(HMC_EARG, "posterior draws: n = %lld is negative", (long long)n);
+  for (int64_t q = 0; indiv && q < n; ++q)
+    if (indiv[q] < i0 || indiv[q] >= i1)
+      return fail(HMC_EARG, "posterior draws: entry %lld: individual %d is outside this rank's shard [%d, %d)", (long long)q,
+                  indiv[q], i0, i1);
+  dr_ms_struct = dr_ms_fb = dr_ms_draw = 0;
+  dr_groups = dr_pruned = 0;
+  if (n == 0) return HMC_OK;
+  auto local = [&](int64_t q) { return indiv ? indiv[q] - i0 : (int)q; };
+  dr.draws = draws;
+  dr.seed = seed;
+  dr.hap = hap;
+  dr.prob = prob;
+  dr.row_off.assign((size_t)nl + 1, 0);
+  for (int64_t q = 0; q < n; ++q) ++dr.row_off[local(q) + 1];
+  for (int i = 0; i < nl; ++i) dr.row_off[i + 1] += dr.row_off[i];
+  dr.rows.assign((size_t)n, 0);
+  {
+    std::vector<int64_t> at(dr.row_off.begin(), dr.row_off.end() - 1);
+    for (int64_t q = 0; q < n; ++q) dr.rows[at[local(q)]++] = q;
+  }
+  dr.status.assign(nl, 1);
+  hipError_t er;
+  if ((er = d_xstatus.ensure(nl)) || (er = d_xre.ensure(nl)) || (er = d_xfmax.ensure(nl))) return hipfail(er, "posterior draws");
+  // the pass counts in the genotype posteriors' fields: theirs are put back
+  const double g_struct = xp_ms_struct, g_fb = xp_ms_fb, g_sites = xp_ms_sites;
+  const int g_groups = xp_groups, g_pruned = xp_pruned;
+  std::vector<char> asked(nl, 0);  // the passes run over the individuals asked for, not the whole shard
+  for (int i = 0; i < nl; ++i) asked[i] = dr.row_off[i + 1] > dr.row_off[i];
+  const int rc = xp_pass(XP_DRAW, "posterior draws", &asked);
+  dr_ms_struct = xp_ms_struct;
+  dr_ms_fb = xp_ms_fb;
+  dr_ms_draw = xp_ms_sites;
+  dr_groups = xp_groups;
+  dr_pruned = xp_pruned;
+  xp_ms_struct = g_struct;
+  xp_ms_fb = g_fb;
+  xp_ms_sites = g_sites;
+  xp_groups = g_groups;
+  xp_pruned = g_pruned;
+  dr.hap = nullptr;
+  dr.prob = nullptr;
+  if (rc) return rc;
+  for (int64_t q = 0; q < n; ++q) {
+    const int i = local(q), stt = dr.status[i];
+    if (status) status[q] = stt;
+    if (stt == 0) continue;
+    // unresolved, or P(genotype) subnormal: the input genotype, as hmc_get_resolutions gives it, at probability 0
+    if (prob) std::fill(prob + q * draws, prob + (q + 1) * draws, 0.0);
+    if (hap)
+      for (int d = 0; d < draws; ++d)
+        for (int side = 0; side < 2; ++side)
+          for (int l = 0; l < L; ++l)
+            hap[(((size_t)q * draws + d) * 2 + side) * L + l] = pan.symbol(l, pan.idx[((size_t)(i0 + i) * 2 + side) * L + l]);
+  }
+  return HMC_OK;
+}
+
 int Ctx::site_group(const ExactArgs &x, int k, int dev_cu) {
   SiteArgs s;
   s.site_off = d_site_off.p;
@@ -612,7 +764,7 @@ void Ctx::site_list(SiteList &sl) const {
   }
 }
 
-int Ctx::xp_pass(XpMode mode, const char *what) {
+int Ctx::xp_pass(XpMode mode, const char *what, const std::vector<char> *only) {
   hipError_t er;
   // What the exact-mode structure pass shares with the E-step and a later call
   // can see is put back afterwards: the last E-step's pass times and counts,
@@ -629,8 +781,9 @@ int Ctx::xp_pass(XpMode mode, const char *what) {
       (er = hipMemcpyAsync(stamps_0, d_stamps.p + 20, sizeof stamps_0, hipMemcpyDeviceToHost, st)) || (er = sync_st()))
     return hipfail(er, what);
   const int n = nloc();
-  std::vector<int32_t> order(n);
-  for (int q = 0; q < n; ++q) order[q] = q;
+  std::vector<int32_t> order;
+  for (int q = 0; q < n; ++q)
+    if (!only || (*only)[q]) order.push_back(q);
   std::stable_sort(order.begin(), order.end(), [&](int x, int y) { return h_cost[x] > h_cost[y]; });
   // The records of a cached exact M-step group are overwritten here, and the
   // posteriors' own group must never be taken for one: no reuse on either side.

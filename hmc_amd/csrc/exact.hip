@@ -32,6 +32,7 @@
 #include "hmc_internal.hpp"
 #include "estep_common.hpp"
 #include "exact.hpp"
+#include "philox.hpp"
 
 namespace hmc {
 
@@ -84,6 +85,8 @@ struct RecView {  // one locus record of the structure pass
 }  // namespace
 
 // Forward and backward likelihoods of every state of every locus (block per individual).
+// BACKWARD = false (ExactArgs::forward_only, the posterior draws) stops after the forward pass.
+template <bool BACKWARD>
 __global__ __launch_bounds__(256) void exact_fb(ExactArgs a) {
   const int tid = threadIdx.x, NT = blockDim.x;
   const int L = a.L, hl = a.head_len;
@@ -138,6 +141,7 @@ __global__ __launch_bounds__(256) void exact_fb(ExactArgs a) {
       if (tid == 0) a.status[bi] = EST_NEEDS_EXACT;
       continue;
     }
+    if (!BACKWARD) continue;
     // backward: states of m_haplopairs[L] keep m_backward_likelihood = 1.0
     {
       const RecView R(a.rec + roff[L], L == hl);
@@ -937,7 +941,8 @@ size_t exact_walk_scratch_doubles(int max_depth, long long span, int width) {
 
 hipError_t launch_exact_fb(const ExactArgs &a, int grid, hipStream_t st) {
   if (a.n_order <= 0) return hipSuccess;
-  hipLaunchKernelGGL(exact_fb, dim3(grid), dim3(256), 0, st, a);
+  if (a.forward_only) hipLaunchKernelGGL(exact_fb<false>, dim3(grid), dim3(256), 0, st, a);
+  else hipLaunchKernelGGL(exact_fb<true>, dim3(grid), dim3(256), 0, st, a);
   return hipGetLastError();
 }
 
@@ -1394,6 +1399,229 @@ hipError_t launch_exact_pair_posteriors(const ExactArgs &a, const PairArgs &s, i
          : ns == 2 ? launch_pair<2>(a, s, grid, st, block)
          : ns == 4 ? launch_pair<4>(a, s, grid, st, block)
                    : launch_pair<8>(a, s, grid, st, block);
+}
+
+// Posterior draws (hmc_posterior_draws): whole haplotype pairs sampled from
+// the exact posterior by backward sampling through the forward values of
+// exact_fb.  A state's forward value is tpv[t] times the sum of its
+// predecessors' forward values over its contributions, so a path is drawn with
+// its posterior probability by choosing the final state in proportion to
+// fwd_L and then, record by record down to the head, one contribution of the
+// current state in proportion to the predecessor's forward value.
+// One lane per draw, 64 consecutive draws of one individual per wavefront,
+// four wavefronts per block; the grid runs over (individual of the group,
+// chunk of 256 draws).  Every choice takes the first index whose running sum
+// exceeds u x (the full sum), else the last index with a positive term:
+//   final record   the F states in chunks of 64: chunk c's sum is the fixed
+//                  butterfly over states 64 c .. 64 c + 63 (zeros past F), the
+//                  chunk prefix S_c = S_c-1 + chunk c's sum in chunk order,
+//                  the full sum S_last.  The block computes the prefix once per
+//                  individual (LDS, or its slice of a device scratch for
+//                  records past DRAW_LDS_CHUNKS chunks — the same doubles); a
+//                  lane searches it for the first chunk with S_c > target and
+//                  then adds that chunk's states to S_c-1 one by one in state
+//                  order;
+//   contributions  of state t at record j, in record order (the order exact_fb
+//                  adds them in): one pass for the full sum, one for the choice.
+// u = draw_uniform(seed, panel index, draw, step) (philox.hpp), step 0 for the
+// final record and 1 + (L - j) at record j: nothing about the launch enters.
+// Haplotypes as estep_traceback spells a candidate: a side parity, flipped by
+// the chosen contribution's rev flag after the state's two alleles are written.
+// prob = ((tpv of the states from record L down to the head, multiplied in
+// that order) x 2 if the two haplotypes differ) / P(genotype).
+__global__ __launch_bounds__(DRAW_BLOCK) void exact_posterior_draws(ExactArgs a, DrawArgs s) {
+  __shared__ double cs_lds[DRAW_LDS_CHUNKS];
+  const int tid = threadIdx.x, lane = tid & (WAVE - 1), wave = tid / WAVE;
+  constexpr int NW = DRAW_BLOCK / WAVE;
+  const int L = a.L, hl = a.head_len, D = s.draws;
+  const int ndc = (D + DRAW_BLOCK - 1) / DRAW_BLOCK;  // chunks of draws per individual
+  const long long items = (long long)a.n_order * ndc;
+  for (long long it = blockIdx.x; it < items; it += gridDim.x) {  // block-uniform
+    const int q = (int)(it / ndc), dc = (int)(it % ndc);
+    const int d = dc * DRAW_BLOCK + tid;
+    const int bi = a.order[q];
+    const int st0 = a.status[bi];
+    const double pg = a.gprob[bi];
+    const bool resolved = (st0 == EST_OK || st0 == EST_OK_PRUNED) && pg > 0.0 && !isinf(pg);
+    if (!resolved || pg < SITE_PG_MIN) {  // the host writes the input genotype: unresolved (1), P(genotype) subnormal (2)
+      if (tid == 0 && dc == 0) s.status[q] = resolved ? 2 : 1;
+      continue;
+    }
+    const unsigned long long *roff = a.rec_off + (size_t)bi * (L + 1);
+    const unsigned long long *xo = a.x_off + (size_t)bi * (L + 1);
+    const RecView RL(a.rec + roff[L], L == hl);
+    const double *fwL = (const double *)(a.x + xo[L]);
+    const int F = RL.F, nc = (F + WAVE - 1) / WAVE;
+    const bool in_lds = nc <= s.lds_chunks && nc <= DRAW_LDS_CHUNKS;
+    if (!in_lds && (!s.csum || nc > s.csum_stride)) {  // (cannot occur: the host sizes the scratch from the group's fmax)
+      if (tid == 0 && dc == 0) s.status[q] = 1;
+      continue;
+    }
+    double *cs = in_lds ? cs_lds : s.csum + (size_t)blockIdx.x * s.csum_stride;
+    __syncthreads();  // the previous item's lanes have read its prefix
+    for (int c = wave; c < nc; c += NW) {
+      const int t = c * WAVE + lane;
+      double part[1] = {t < F ? fwL[t] : 0.0};
+      const double v = group_sum_fixed<WAVE>(part);
+      if (lane == 0) cs[c] = v;
+    }
+    __syncthreads();
+    if (tid == 0) {
+      double r = 0.0;
+      for (int c = 0; c < nc; ++c) {
+        r += cs[c];
+        cs[c] = r;
+      }
+    }
+    __syncthreads();
+    if (d >= D) continue;  // (the barriers above are passed by every thread of the block)
+    const uint32_t pi = (uint32_t)(s.indiv0 + bi), du = (uint32_t)d;
+    auto put = [&](int k, int side, uint32_t x) {
+      if (s.al) s.al[(((size_t)q * 2 + side) * L + k) * D + d] = (uint8_t)x;
+    };
+    int t;
+    {  // the final state
+      const double target = draw_uniform(s.seed, pi, du, 0u) * cs[nc - 1];
+      int lo = 0, hi = nc - 1;  // S_last > target: u < 1
+      while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (cs[mid] > target) hi = mid;
+        else lo = mid + 1;
+      }
+      double run = lo > 0 ? cs[lo - 1] : 0.0;
+      const int t1 = min(F, (lo + 1) * WAVE);
+      int pick = -1, last = lo * WAVE;
+      for (int x = lo * WAVE; x < t1; ++x) {
+        const double v = fwL[x];
+        run += v;
+        if (v > 0.0) last = x;
+        if (run > target) {
+          pick = x;
+          break;
+        }
+      }
+      t = pick >= 0 ? pick : last;
+    }
+    int par = 0;
+    bool het = false, dead = false;
+    double p = 1.0;
+    for (int j = L; j > hl; --j) {
+      const RecView R(a.rec + roff[j], false);
+      const uint32_t hd = R.hdr[t], xa = hd & 0xFFu, xb = (hd >> 8) & 0xFFu;
+      const uint32_t r0 = R.cb[t], r1 = R.cb[t + 1];
+      const double tpv = R.tpv[t];
+      const double *fp = (const double *)(a.x + xo[j - 1]);
+      put(j - 1, par, xa);
+      put(j - 1, par ^ 1, xb);
+      het |= xa != xb;
+      p = j == L ? tpv : p * tpv;
+      // the full sum: four contributions at a time, their words, then their
+      // predecessors' forward values, then the terms in record order
+      double tot = 0.0;
+      for (uint32_t r = r0; r < r1; r += 4) {
+        uint32_t wv[4];
+        double fv[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) wv[k] = r + k < r1 ? R.ct[r + k] : 0u;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) fv[k] = r + k < r1 ? fp[cw_state(wv[k])] : 0.0;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) tot += fv[k];
+      }
+      const double target = draw_uniform(s.seed, pi, du, (uint32_t)(1 + (L - j))) * tot;
+      double run = 0.0;
+      uint32_t wsel = 0u, wlast = 0u;
+      bool got = false, any = false;
+      for (uint32_t r = r0; r < r1; ++r) {
+        const uint32_t w = R.ct[r];
+        const double v = fp[cw_state(w)];
+        run += v;
+        if (v > 0.0) {
+          wlast = w;
+          any = true;
+        }
+        if (run > target) {
+          wsel = w;
+          got = true;
+          break;
+        }
+      }
+      if (!got) {
+        if (!any) {  // (a state no path reaches: a zero term is never chosen, so no draw arrives here;
+                     // if one did, the individual counts as unresolved and the host writes its input genotype)
+          dead = true;
+          s.status[q] = 1;
+          break;
+        }
+        wsel = wlast;
+      }
+      if (cw_rev(wsel)) par ^= 1;
+      t = (int)cw_state(wsel);
+    }
+    if (!dead) {  // the head state: loci below head_len
+      const RecView H(a.rec + roff[hl], true);
+      const double tpv = H.tpv[t];
+      p = L == hl ? tpv : p * tpv;
+      if (hl == 1) {
+        const uint32_t hd = H.hdr[t], xa = hd & 0xFFu, xb = (hd >> 8) & 0xFFu;
+        put(0, par, xa);
+        put(0, par ^ 1, xb);
+        het |= xa != xb;
+      } else {
+        const uint32_t *plo = H.cb + H.F + 1, *phi = plo + H.F;
+        const uint8_t *pa = a.head_al + (size_t)plo[t] * hl, *pb = a.head_al + (size_t)phi[t] * hl;
+        for (int k = 0; k < hl; ++k) {
+          put(k, par, pa[k]);
+          put(k, par ^ 1, pb[k]);
+          het |= pa[k] != pb[k];
+        }
+      }
+    }
+    if (s.prob) s.prob[(size_t)q * D + d] = dead ? 0.0 : (het ? p * 2.0 : p) / pg;
+  }
+}
+
+hipError_t launch_exact_posterior_draws(const ExactArgs &a, const DrawArgs &s, int grid, hipStream_t st) {
+  if (a.n_order <= 0) return hipSuccess;
+  if (grid < 1 || s.draws < 1 || !s.status || s.lds_chunks < 0 ||
+      s.lds_chunks > DRAW_LDS_CHUNKS || (s.csum && s.csum_stride < 1))
+    return hipErrorInvalidValue;
+  hipLaunchKernelGGL(exact_posterior_draws, dim3(grid), dim3(DRAW_BLOCK), 0, st, a, s);
+  return hipGetLastError();
+}
+
+// The draws' allele indices al[slot][side][locus][draw] (bytes, as the lanes
+// of exact_posterior_draws store them) into the caller's layout
+// hap[slot][draw][side][locus] as symbols of sym[locus][width]: tiles of 64
+// loci x 64 draws through LDS, read along the draws and written along the
+// loci.  A byte that is no allele index (an individual the draw kernel left
+// unwritten: status 1 or 2) becomes -1; the host overwrites those rows.
+__global__ __launch_bounds__(256) void draws_to_symbols(const uint8_t *al, const int32_t *sym, int32_t *hap, int L, int D, int W) {
+  __shared__ uint8_t tile[64][65];
+  const size_t us = blockIdx.x;  // slot * 2 + side
+  const int l0 = blockIdx.y * 64, d0 = blockIdx.z * 64;
+  for (int k = threadIdx.x; k < 64 * 64; k += 256) {
+    const int l = k / 64, d = k % 64;
+    if (l0 + l < L && d0 + d < D) tile[l][d] = al[(us * L + l0 + l) * D + d0 + d];
+  }
+  __syncthreads();
+  const size_t slot = us >> 1, side = us & 1;
+  for (int k = threadIdx.x; k < 64 * 64; k += 256) {
+    const int d = k / 64, l = k % 64;
+    if (l0 + l < L && d0 + d < D) {
+      const int x = tile[l][d];
+      hap[((slot * D + d0 + d) * 2 + side) * L + l0 + l] = x < W ? sym[(size_t)(l0 + l) * W + x] : -1;
+    }
+  }
+}
+
+hipError_t launch_draws_to_symbols(const uint8_t *al, const int32_t *sym, int32_t *hap, int slots, int L, int D, int W,
+                                   hipStream_t st) {
+  if (slots <= 0) return hipSuccess;
+  const int gy = (L + 63) / 64, gz = (D + 63) / 64;
+  if (!al || !sym || !hap || L < 1 || D < 1 || W < 1 || gy > 65535 || gz > 65535) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(draws_to_symbols, dim3(2u * (unsigned)slots, gy, gz), dim3(256), 0, st, al, sym, hap, L, D, W);
+  return hipGetLastError();
 }
 
 }  // namespace hmc

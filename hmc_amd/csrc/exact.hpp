@@ -36,6 +36,7 @@ struct ExactArgs {
   unsigned *span_max = nullptr;    // exact_span: atomicMax of each individual's largest span (zeroed by the host)
   unsigned long long *acc_freq, *acc_prefix;  // [candidates] fixed point
   long long item0 = 0, item1 = -1;  // walk items [item0, item1) of n_order x L (individual-major); -1 = all
+  bool forward_only = false;        // exact_fb leaves the backward values unwritten (the posterior draws never read them)
 };
 
 // Breadth-first trie walk (exact_walk_units): one lane per work unit — a trie
@@ -161,5 +162,33 @@ constexpr int pair_tier_max(int ns) { return 65024 / (32 * ns); }  // 2032, 1016
 constexpr int PAIR_TIER_DEFAULT = pair_tier_max(PAIR_SLOTS_MAX);
 // after exact_fb over the same group; NS, block sizes 64 .. 256 and the grid do not change the bits
 hipError_t launch_exact_pair_posteriors(const ExactArgs &a, const PairArgs &s, int ns, int grid, hipStream_t st, int block = 256);
+
+// Posterior draws (exact_posterior_draws): `draws` lattice paths per
+// individual of the group, sampled backwards through the forward values
+// exact_fb left in the x-store.  Individual q of the group (ExactArgs::order)
+// owns output slot q.  The lanes store allele indices draw-minor,
+// al[slot][side][locus][draw] bytes, so the 64 lanes of a wavefront (64
+// consecutive draws) store adjacent bytes; draws_to_symbols or the host copy
+// turns them into the caller's [slot][draw][side][locus] symbols.  al may be
+// NULL (no haplotypes asked for).  status is zeroed by the caller: the kernel
+// writes the non-zero ones only.
+struct DrawArgs {
+  int draws = 0;
+  unsigned long long seed = 0;
+  int indiv0 = 0;                  // panel index of batch index 0 (the shard's first individual)
+  uint8_t *al = nullptr;           // [slots][2][L][draws] allele indices
+  double *prob = nullptr;          // [slots][draws]
+  int32_t *status = nullptr;       // [slots] 0 ok, 1 unresolved, 2 P(genotype) subnormal
+  double *csum = nullptr;          // [grid][csum_stride]: the final record's chunk prefix sums past the LDS tier
+  int csum_stride = 0;             // chunks of 64 states of the group's largest record
+  int lds_chunks = 0;              // final records of at most this many chunks keep their prefix sums in LDS (0: none do)
+};
+constexpr int DRAW_BLOCK = 256;        // draws per block: four wavefronts of 64
+constexpr int DRAW_LDS_CHUNKS = 1024;  // final records of up to 65 536 states keep their prefix sums in LDS (8 KiB)
+// after exact_fb over the same group; the grid does not change the bits
+hipError_t launch_exact_posterior_draws(const ExactArgs &a, const DrawArgs &s, int grid, hipStream_t st);
+// al[slots][2][L][D] allele indices -> hap[slots][D][2][L] symbols of sym[L][W] (64 x 64 tiles through LDS)
+hipError_t launch_draws_to_symbols(const uint8_t *al, const int32_t *sym, int32_t *hap, int slots, int L, int D, int W,
+                                   hipStream_t st);
 
 }  // namespace hmc

@@ -603,6 +603,47 @@ class HaploModel:
         """pair_posteriors of pair_span_list(span) as text, one line per query of status 0 (hmc_write_pair_posteriors)."""
         self._check(lib().hmc_write_pair_posteriors(self._h, path.encode(), int(span)))
 
+    def posterior_draws(self, draws: int, seed: int, indiv=None) -> dict:
+        """Whole haplotype pairs sampled from the exact posterior under the
+        model of the last resolve_all (hmc_posterior_draws): for the panel
+        indices `indiv` (any order, repeats allowed; None = this rank's whole
+        shard) hap[n, draws, 2, L] symbols, prob[n, draws] = the exact
+        posterior of each drawn unordered pair, status[n] (0 ok; 1 individual
+        unresolved, 2 its P(genotype) subnormal: the input genotype in every
+        draw, prob 0).  Draw d of an individual depends on the model, the
+        seed, the individual and d alone."""
+        if indiv is None:
+            qi, n = None, self.i1 - self.i0
+        else:
+            qi = np.ascontiguousarray(indiv, np.int32).reshape(-1)
+            n = len(qi)
+        D = max(int(draws), 0)
+        out = dict(hap=np.zeros((n, D, 2, self.L), np.int32), prob=np.zeros((n, D), np.float64),
+                   status=np.zeros(n, np.int32))
+        self._check(lib().hmc_posterior_draws(self._h, n, None if qi is None else _p(qi, C.c_int32), int(draws),
+                                              C.c_uint64(int(seed)), _p(out["hap"], C.c_int32), _p(out["prob"], C.c_double),
+                                              _p(out["status"], C.c_int32)))
+        return out
+
+    def draw_stats(self) -> dict:
+        """Device ms and counts of the last posterior_draws (hmc_last_draw_stats)."""
+        s, f, k = C.c_double(), C.c_double(), C.c_double()
+        g, p = C.c_int(), C.c_int()
+        self._check(lib().hmc_last_draw_stats(self._h, C.byref(s), C.byref(f), C.byref(k), C.byref(g), C.byref(p)))
+        return dict(structure_ms=s.value, fb_ms=f.value, draw_ms=k.value, groups=g.value, n_pruned=p.value)
+
+    def set_draw_tuning(self, lds_chunks: int = -1, forward_only: bool = True):
+        """Test seam of posterior_draws (hmc_set_draw_tuning): the final
+        record's prefix sums stay in LDS up to this many chunks of 64 states
+        (-1 = default, 0 = always the device scratch); forward_only: the
+        call's forward-backward kernel skips its backward half.  Results do
+        not depend on it."""
+        self._check(lib().hmc_set_draw_tuning(self._h, int(lds_chunks), 1 if forward_only else 0))
+
+    def write_posterior_draws(self, path: str, draws: int = 100, seed: int = 0):
+        """posterior_draws of the whole shard as text, one line per individual of status 0 and draw (hmc_write_posterior_draws)."""
+        self._check(lib().hmc_write_posterior_draws(self._h, path.encode(), int(draws), C.c_uint64(int(seed))))
+
     def timings(self) -> dict:
         f, t, m = C.c_double(), C.c_double(), C.c_double()
         self._check(lib().hmc_last_timings(self._h, C.byref(f), C.byref(t), C.byref(m)))

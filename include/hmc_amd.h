@@ -354,6 +354,83 @@ int hmc_pair_span_list(hmc_ctx *ctx, int span, int64_t *n, int32_t *indiv, int32
  * individual took.  Replaces no reference interface. */
 int hmc_last_pair_stats(const hmc_ctx *ctx, double *structure_ms, double *fb_ms, double *sweep_ms, int *groups, int *n_pruned,
                         int *n_spilled, int *slots, int *max_rounds);
+/* Posterior draws: whole haplotype pairs sampled from the exact posterior
+ * P(pair | genotype) under the model of the last E-step — what multiple
+ * imputation and the posterior of any statistic that is no one- or two-locus
+ * marginal need.  (hmc_get_samples is the E-step's truncated, deterministic
+ * k-best list, not a sample; "samples" keeps meaning those.)
+ * indiv[n] are panel indices inside this rank's shard, in any order, repeats
+ * allowed; indiv = NULL means the whole shard (n is ignored).  Outputs, any of
+ * which may be NULL: hap[n][draws][2][L] symbols, prob[n][draws], status[n].
+ * status 0 ok; 1 the individual is unresolved; 2 its P(genotype) is below
+ * DBL_MIN (as hmc_genotype_posteriors).  Rows of status 1 and 2 carry the
+ * input genotype in every draw (as hmc_get_resolutions does for unresolved
+ * individuals) and prob 0.
+ *
+ * One draw is one path through the forward lattice.  Record j (head_len <= j
+ * <= L) holds the states after j loci; a state t has a transition product
+ * tpv[t] and, above the head record, a list of contributions in record order,
+ * each naming a predecessor state of record j - 1 and a rev flag; fwd_j[t] is
+ * the forward likelihood exact_fb computes (tpv[t] times the sum of the
+ * predecessors' fwd in list order; at the head record tpv[t], doubled for a
+ * heterozygous head pair).
+ *   Selection rule, used for every choice: given terms x_0, x_1, ... >= 0 in a
+ *   fixed order, a full sum T and a uniform u, take the first index whose
+ *   running sum exceeds u * T (one rounded product); if none does, the last
+ *   index with a positive term.  A term of 0 is never chosen.
+ *   Final record (step 0): terms fwd_L[t] in state order, F states in chunks
+ *   of 64.  Chunk c's sum is the butterfly sum of its 64 values (zeros past
+ *   F): v[i] += v[i ^ 32], then ^ 16, 8, 4, 2, 1.  The chunk prefix is S_c =
+ *   S_c-1 + (chunk c's sum), in chunk order from S_-1 = 0, and T = S_last.
+ *   The chunk is the first with S_c > u * T; inside it the running sum starts
+ *   at S_c-1 and adds fwd_L[t] state by state, and the rule above picks t
+ *   among the chunk's states.
+ *   Record j = L, L - 1, ..., head_len + 1 (step 1 + (L - j)), current state
+ *   t: terms fwd_(j-1)[pred(r)] over t's contributions r in record order, T
+ *   their sum accumulated from 0 in that order (the common factor tpv[t]
+ *   cancels), the running sum likewise.  The chosen contribution's
+ *   predecessor is the state at record j - 1.
+ *   Uniforms: Philox4x32-10 with key (seed & 0xFFFFFFFF, seed >> 32) and
+ *   counter (step, draw index, panel index of the individual, 0) gives words
+ *   w0..w3; u = ((w0 >> 5) * 2^26 + (w1 >> 6)) * 2^-53, in [0, 1).
+ *   Haplotypes, as the E-step's traceback spells a candidate: a side parity
+ *   starts at 0; at record j the state's two alleles (a, b) of locus j - 1 go
+ *   to haplotypes (parity, 1 - parity), then the parity flips if the chosen
+ *   contribution has rev set.  The head state supplies loci below head_len
+ *   from its two head patterns.  Which of a draw's two haplotypes comes first
+ *   carries no information.
+ *   prob = the exact posterior of the unordered pair drawn: p = tpv of the
+ *   final state, times tpv of each chosen state from record L - 1 down to the
+ *   head record, one multiplication each in that order; doubled if the two
+ *   haplotypes differ at any locus; divided by the last E-step's P(genotype)
+ *   (hmc_get_estep's total).  A heterozygous pair with a homozygous prefix is
+ *   reached by two paths (rev or not out of the homozygous state), each with
+ *   half of it; a heterozygous head carries the factor 2 itself; a homozygous
+ *   pair has one path: the factor belongs to the pair, not the path.
+ * So a draw's bits depend on the model and on (seed, individual, draw index)
+ * alone: not on `draws` (draw d of 8 is draw d of 8 192), the other
+ * individuals of the call, sharding, launch shapes, store budgets or groups.
+ * An individual with a missing allele at a head locus draws its loci below
+ * head_len from the reference's head pairing (initHeadList, HaploBuilder.cpp:
+ * 153-224), which is not a phasing model.
+ * Needs a preceding hmc_resolve_all (any E-step mode); runs its own exact-mode
+ * structure pass and forward pass, over the individuals asked for only, and
+ * changes no later result.  The kernel stores allele indices draw-minor and a
+ * second kernel transposes them into hap's layout as symbols; the individuals
+ * go through the device in batches whose outputs take at most 512 MiB (one
+ * individual at least: 8 draws + 10 draws L bytes each), so the host memory a
+ * call needs is the caller's three outputs plus one batch of prob.  n = 0 is
+ * HMC_OK with no device work.  HMC_EARG when no E-step has run or the model
+ * has changed since the last one, with a message naming the first individual
+ * outside the shard, or for draws < 1; HMC_EUNSUPPORTED as for
+ * hmc_genotype_posteriors.
+ * Replaces no reference interface. */
+int hmc_posterior_draws(hmc_ctx *ctx, int64_t n, const int32_t *indiv, int draws, uint64_t seed, int32_t *hap, double *prob,
+                        int32_t *status);
+/* Last hmc_posterior_draws: device ms of its structure passes, of the forward
+ * kernel and of the draw kernel with its transposition; groups the individuals ran in;
+ * individuals on pruned records.  Replaces no reference interface. */
+int hmc_last_draw_stats(const hmc_ctx *ctx, double *structure_ms, double *fb_ms, double *draw_ms, int *groups, int *n_pruned);
 /* ---- whole EM: HaploModel::run (HaploModel.cpp:117-155) ------------------ */
 typedef struct hmc_iter_log {
   double log_likelihood;
@@ -460,6 +537,15 @@ int hmc_write_switch_posteriors(hmc_ctx *ctx, const char *path);
  * preceding hmc_resolve_all or hmc_run; HMC_EARG for span < 1.
  * Replaces no reference interface. */
 int hmc_write_pair_posteriors(hmc_ctx *ctx, const char *path, int span);
+/* hmc_posterior_draws of the whole shard as text (hmc_resolve --output-draws
+ * FILE --draws D --seed S): the header
+ * "Id\tDraw\tPosterior\tHaplotype0\tHaplotype1", then one line per individual
+ * of status 0 and per draw, individual-major: the individual's id, the draw
+ * index, the pair's posterior as %.17g (reads back to the same double), and
+ * each haplotype as its alleles, spelled as the genotype files spell them and
+ * separated by single spaces.  Needs a preceding hmc_resolve_all or hmc_run;
+ * HMC_EARG for draws < 1.  Replaces no reference interface. */
+int hmc_write_posterior_draws(hmc_ctx *ctx, const char *path, int draws, uint64_t seed);
 /* ---- tuning -------------------------------------------------------------- */
 /* frontier_cap: initial states per locus and individual (doubles on
  * overflow, at most 2 097 151); trace_bytes: trace-store budget (0 =
@@ -652,6 +738,10 @@ int hmc_test_coop_nth_element(int device, double *lik, uint32_t *tag, const int3
 enum { HMC_SELECT_PAIR = 0, HMC_SELECT_PAIR10 = 1, HMC_SELECT_WIDE = 2, HMC_SELECT_RANK = 3 };
 int hmc_test_coop_select(int device, int mode, int width, double *lik, uint32_t *tag, const int32_t *n,
                          const int32_t *nth, double *tie, int count);
+/* The uniform hmc_posterior_draws uses for decision `step` of draw `draw` of
+ * the individual with panel index `indiv` (philox.hpp: Philox4x32-10, key =
+ * the two halves of seed, counter = (step, draw, indiv, 0)), on the host. */
+double hmc_test_draw_uniform(uint64_t seed, int32_t indiv, int32_t draw, int32_t step);
 /* Library version string. */
 const char *hmc_version(void);
 /* Version, target, flags and build time of this libhmc_amd.so (bench.py

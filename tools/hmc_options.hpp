@@ -18,6 +18,10 @@ struct Options {
   std::string output_pair_posteriors;  // --output-pair-posteriors FILE
   int pair_span = 0;                   // --pair-span K (required with it, >= 1)
   bool have_pair_span = false;
+  std::string output_draws;            // --output-draws FILE
+  int draws = 100;                     // --draws D (>= 1)
+  unsigned long long seed = 0;         // --seed S
+  bool have_draws = false, have_seed = false;
 };
 
 // --output-posteriors (no reference counterpart): <first file>.posteriors, the
@@ -45,7 +49,10 @@ constexpr const char *USAGE =
     "                        loci of an individual, the probability that their lower alleles share a\n"
     "                        haplotype (cis) and that they do not (trans), under the final model\n"
     "  --output-pair-posteriors FILE --pair-span K  write FILE: cis and trans for every pair of an\n"
-    "                        individual's heterozygous loci at most K heterozygous loci apart (K >= 1)";
+    "                        individual's heterozygous loci at most K heterozygous loci apart (K >= 1)\n"
+    "  --output-draws FILE [--draws D] [--seed S]  write FILE: D haplotype pairs per individual drawn\n"
+    "                        from the exact posterior under the final model, each with its posterior\n"
+    "                        (default D = 100, S = 0; a draw depends on S, the individual and its index)";
 
 // 0 on success; otherwise `err` says what is wrong (a missing value, an
 // unknown option, no data file).
@@ -76,6 +83,9 @@ inline int parse_options(int argc, const char *const *argv, Options &o, std::str
     else if (a == "--output-switch-posteriors") o.output_switch_posteriors = true;
     else if (a == "--output-pair-posteriors") { if (!next()) return 1; o.output_pair_posteriors = v; }
     else if (a == "--pair-span") { if (!next()) return 1; o.pair_span = atoi(v); o.have_pair_span = true; }
+    else if (a == "--output-draws") { if (!next()) return 1; o.output_draws = v; }
+    else if (a == "--draws") { if (!next()) return 1; o.draws = atoi(v); o.have_draws = true; }
+    else if (a == "--seed") { if (!next()) return 1; o.seed = strtoull(v, nullptr, 10); o.have_seed = true; }
     else if (a == "-m" || a == "--model") { if (!next()) return 1; o.model = v; }          // HMC.cpp:35
     else if (a == "-o" || a == "--mc-order") { if (!next()) return 1; o.mc_order = atoi(v); }      // HMC.cpp:41
     else if (a == "-n" || a == "--num-patterns") { if (!next()) return 1; o.num_patterns = atoi(v); }  // HMC.cpp:38
@@ -92,6 +102,14 @@ inline int parse_options(int argc, const char *const *argv, Options &o, std::str
   }
   if (o.have_pair_span && o.output_pair_posteriors.empty()) {
     err = "--pair-span needs --output-pair-posteriors FILE\n" + std::string(USAGE);
+    return 1;
+  }
+  if (!o.output_draws.empty() && o.draws < 1) {
+    err = "--output-draws needs --draws D with D >= 1\n" + std::string(USAGE);
+    return 1;
+  }
+  if ((o.have_draws || o.have_seed) && o.output_draws.empty()) {
+    err = "--draws and --seed need --output-draws FILE\n" + std::string(USAGE);
     return 1;
   }
   return 0;

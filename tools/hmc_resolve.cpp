@@ -11,7 +11,8 @@
 //               [-m MV|MC|MA] [-o mc_order] [--exact-estimate] [-i 1]
 //               [--sample-size 10] [--min-pattern-len 1] [--max-pattern-len 30]
 //               [--output-patterns x] [--output-posteriors] [--output-switch-posteriors]
-//               [--output-pair-posteriors FILE --pair-span K] [--device 0] datafile ...
+//               [--output-pair-posteriors FILE --pair-span K]
+//               [--output-draws FILE [--draws 100] [--seed 0]] [--device 0] datafile ...
 // --output-posteriors (no reference counterpart) writes <first file>.posteriors:
 // genotype posteriors at the loci with a missing input allele, under the final
 // model (hmc_write_posteriors).  --output-switch-posteriors (none either)
@@ -20,6 +21,9 @@
 // --output-pair-posteriors FILE --pair-span K (none either) writes FILE: cis
 // and trans for every pair of an individual's heterozygous loci at most K
 // heterozygous loci apart (hmc_write_pair_posteriors).
+// --output-draws FILE [--draws D] [--seed S] (none either) writes FILE: D
+// haplotype pairs per individual drawn from the exact posterior under the
+// final model, each with its posterior (hmc_write_posterior_draws).
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -96,6 +100,9 @@ int main(int argc, char **argv) {
   }
   if (!o.output_pair_posteriors.empty()) {  // of the same E-step
     if ((rc = hmc_write_pair_posteriors(ctx, o.output_pair_posteriors.c_str(), o.pair_span))) die("hmc_write_pair_posteriors");
+  }
+  if (!o.output_draws.empty()) {  // of the same E-step
+    if ((rc = hmc_write_posterior_draws(ctx, o.output_draws.c_str(), o.draws, o.seed))) die("hmc_write_posterior_draws");
   }
   hmc_ctx_destroy(ctx);
   return 0;
