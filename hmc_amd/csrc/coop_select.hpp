@@ -19,6 +19,24 @@
 // numbers its stops (ballot + popcount), the stops publish their positions in
 // two small LDS arrays, and every stop reads its partner: one shuffle then
 // moves all swapped elements.
+//
+// Which stops swap follows from the stop counts alone, before any position is
+// published.  With Lw / Rw the stop masks, kL(x) = |Lw below x| and
+// above(x) = |Rw strictly above x|:
+//   a left stop at x (it is l_kL) swaps   iff  above(x) > kL(x)
+//   a right stop at x (it is r_above) swaps iff  kL(x) > above(x)
+// since l_kL < r_kL says that more than kL right stops lie strictly above x,
+// and l_above < x says that more than above(x) left stops lie strictly below
+// x.  (In the loop's older names, kR = nR - 1 - |Rw below x| is above(x) +
+// [x in Rw], which gives lsw = isL && kR - isR >= kL, rsw = isR && kL > kR.)
+// `first` is always a right stop, the last one (r_{nR-1}); no left stop lies
+// below it, so it never swaps and no swapping left stop is paired with it:
+// the loops leave it out of Rw, which changes no above(x) for x > first.
+// K = the number of swapping left stops, known before the LDS exchange; the
+// right stops are published behind a sentinel (rp[0] = 64 = r_{-1}, rp[k + 1]
+// = r_k), so the partner positions and the two cut candidates lp[K], rp[K] are
+// read in one batch with indices that need no clamp (all are < the segment's
+// slot count: kL < x, above <= |Rw| <= slots - 1, K <= |Lw| <= slots - 1).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstdint>
@@ -52,6 +70,16 @@ __device__ inline void wave_lds_sync() {
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
   __builtin_amdgcn_wave_barrier();
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+// Keeps a batch of LDS reads where it is written: the values count as used
+// here, so no read is sunk behind the branch of the one select that consumes
+// it (which would put it after the others in an exec-masked block of its own).
+__device__ inline void lds_batch(int &a, int &b, int &c, int &d) {
+  asm volatile("" : "+v"(a), "+v"(b), "+v"(c), "+v"(d));
+}
+__device__ inline void lds_batch(int &a, int &b, int &c, int &d, int &e, int &f) {
+  asm volatile("" : "+v"(a), "+v"(b), "+v"(c), "+v"(d), "+v"(e), "+v"(f));
 }
 
 // This lane's place in the segmentation (SW lanes per segment, G segments).
@@ -95,9 +123,11 @@ __device__ inline int seg_lowest(uint32_t bits) {
 }
 
 // LDS scratch of the segmented selection, one entry per lane (segment g uses
-// [base, base+SW)): left-stop and right-stop positions, a per-lane junk slot
-// pair that absorbs the writes of lanes that are not stops, and a spill list
-// for the heap-select path.
+// [base, base+SW)): left-stop and right-stop positions (rpos: a sentinel,
+// then the stops), per-lane junk slots that absorb the writes of lanes that
+// are not stops (the selections use the first 64: the slots are never read,
+// and each write instruction hits a lane's slot once), and a spill list for
+// the heap-select path.
 struct SegScratch {
   int *lpos;      // [64]
   int *rpos;      // [64]
@@ -111,10 +141,14 @@ struct SegScratch {
 // g*SW + k; n, nth uniform inside a segment, n <= SW <= 64; n == 0 marks an
 // idle segment).  Whole-wave call, branch-free per lane for SW <= 32.
 //
-// One partition costs two LDS round trips: one batch that reads the median
-// candidates, the value at `first` and every lane's own element, and the stop
-// pairing; each lane then writes its element straight into its destination
-// slot (the LDS executes a wave's accesses in order, so no wait).  The median
+// One partition costs two dependent LDS round trips: one batch that reads the
+// median candidates, the value at `first` and every lane's own element, and
+// one batch behind the stops' position writes that reads the partner
+// positions together with the two cut candidates (the swap decisions and K
+// come from the stop counts, so nothing in that batch waits on another read;
+// the cut used to be a third trip behind a ballot of the partner test).  Each
+// lane then writes its element straight into its destination slot (the LDS
+// executes a wave's accesses in order, so no wait).  The median
 // swap (std::__move_median_to_first) is not executed as a data move: the
 // ballots are taken over *positions* (lane p evaluates the value position p
 // holds after the swap: the pivot at `first`, first's value at r), and each
@@ -135,13 +169,18 @@ __device__ inline void seg_nth_slots(int n, int nth, const Seg &sg, const SegScr
   double *sl = ss.slik + sg.base;
   uint32_t *sm = ss.smeta + sg.base;
   int *lp = ss.lpos + sg.base, *rp = ss.rpos + sg.base;
-  int *jl = ss.junk + lane, *jr = ss.junk + 64 + lane;
+  int *jk = ss.junk + lane;  // never read: absorbs the writes of lanes that are not stops
   const int kmax = sg.sw - 1;
+  const uint64_t b_act = wave_ballot(act);
+  if (k == 0) rp[0] = 64;  // r_{-1}: stays for the whole call (stops go to rp[1 ..])
   while (true) {
     // a segment whose depth budget is spent stops here with > 3 elements left
     // and finishes with the heap select below (its range no longer changes)
     const bool part = act && last - first > 3 && depth > 0;
-    if (!wave_ballot(part)) break;
+    // each ballot of a single comparison stays a lane mask; the conjunctions
+    // are scalar ANDs (a ballot of a && b would be materialised and re-compared)
+    const uint64_t b_part = b_act & wave_ballot(last - first > 3) & wave_ballot(depth > 0);
+    if (!b_part) break;
     depth -= part ? 1 : 0;
     // std::__move_median_to_first(first, first+1, mid, last-1) (stl_algo.h:79-102)
     const int a = first + 1, b = first + ((last - first) >> 1), c = last > 0 ? last - 1 : 0;
@@ -149,47 +188,44 @@ __device__ inline void seg_nth_slots(int n, int nth, const Seg &sg, const SegScr
     const double v = sl[k];
     const uint32_t m = sm[k];
     // which of a (0), b (1), c (2) is the median, as a table over the three
-    // comparisons (index ab*4 + bc*2 + ac) so it compiles to selects
+    // comparisons (index ab*4 + bc*2 + ac) so it compiles to selects; `first`
+    // (the identity) in a segment that sits this round out
     const int idx = (va > vb ? 4 : 0) | (vb > vc ? 2 : 0) | (va > vc ? 1 : 0);
     const int w = (22561 >> (2 * idx)) & 3;
-    const int r = w == 0 ? a : (w == 1 ? b : c);
+    const int r = !part ? first : (w == 0 ? a : (w == 1 ? b : c));
     const double pivot = w == 0 ? va : (w == 1 ? vb : vc);
     // stops by position (std::__unguarded_partition, stl_algo.h:1878-1896):
     // left scan over [first+1, last) stops at !(x > pivot), right scan over
-    // [first, last) at !(pivot > x)
+    // [first, last) at !(pivot > x); `first`, always a right stop, never swaps
+    // and is left out of Rw
     const double pv = k == first ? pivot : (k == r ? vf : v);
-    // each ballot of a single comparison stays a lane mask; the conjunctions
-    // are scalar ANDs (a ballot of a && b would be materialised and re-compared)
-    const uint64_t b_part = wave_ballot(part), b_in = wave_ballot(k > first) & wave_ballot(k < last);
-    const uint64_t b_first = wave_ballot(k == first);
-    const uint64_t b_le = wave_ballot(!(pv > pivot)), b_ge = wave_ballot(!(pivot > pv));
-    const uint32_t Lw = seg_bits(b_part & b_in & b_le, sg);
-    const uint32_t Rw = seg_bits(b_part & (b_in | b_first) & b_ge, sg);
-    const int nL = __popc(Lw), nR = __popc(Rw);
+    const uint64_t b_in = b_part & wave_ballot(k > first) & wave_ballot(k < last);
+    const uint32_t Lw = seg_bits(b_in & wave_ballot(!(pv > pivot)), sg);
+    const uint32_t Rw = seg_bits(b_in & wave_ballot(!(pivot > pv)), sg);
+    const int nL = __popc(Lw);
     // this lane's element is at position x once the median is at first
-    const int x = !part ? k : (k == first ? r : (k == r ? first : k));
-    const uint32_t xb = (1u << x) - 1u;
-    const bool isL = part && ((Lw >> x) & 1u), isR = part && ((Rw >> x) & 1u);
-    const int kL = __popc(Lw & xb);
-    const int kR = nR - 1 - __popc(Rw & xb);
-    *(isL ? lp + kL : jl) = x;
-    *(isR ? rp + kR : jr) = x;
+    const int x = k == first ? r : (k == r ? first : k);
+    const bool isL = (Lw >> x) & 1u, isR = (Rw >> x) & 1u;
+    // left stops below x and right stops above x: the pair index of a stop of
+    // either kind, and the swap decision (header comment)
+    const int kL = __popc(Lw & ((1u << x) - 1u));
+    const int kR = __popc((Rw >> 1) >> x);
+    const bool lsw = isL && kR > kL, rsw = isR && kL > kR;
+    const int K = __popcll(wave_ballot(isL) & wave_ballot(kR > kL) & sg.mask);
+    *(isL ? lp + kL : jk) = x;
+    *(isR ? rp + 1 + kR : jk) = x;
     wave_lds_sync();
-    const int qR = rp[kL < kmax ? kL : kmax];
-    const int qL = lp[kR < 0 ? 0 : (kR < kmax ? kR : kmax)];
-    // pair k swaps iff l_k < r_k; both roles are checked, a position swaps at most once
-    const bool lsw = isL && kL < nR && x < qR;
-    const bool rsw = isR && kR < nL && qL < x;
+    // one batch: the partners and the cut = min(l_K, r_{K-1}), the first left
+    // stop that does not swap and the lowest right stop that does.  Every
+    // index is inside the segment (kL < x, kR and K < sw); a lane that does
+    // not swap reads a slot it does not use.
+    int qR = rp[1 + kL], qL = lp[kR];
+    int lKs = lp[K], rK = rp[K];
+    lds_batch(qR, qL, lKs, rK);
     const int dest = lsw ? qR : (rsw ? qL : x);
     sl[dest] = v;
     sm[dest] = m;
-    // cut = min(l_K, r_{K-1}): the first left stop that does not swap and the
-    // lowest right stop that does.  The swaps are a prefix of the stop pairs,
-    // so with K = the number of swapping pairs both come from the stop
-    // positions still in lp / rp.
-    const int K = __popcll(wave_ballot(lsw) & sg.mask);
-    const int lK = K < nL ? lp[K < kmax ? K : kmax] : 64;
-    const int rK = K > 0 ? rp[K - 1 < kmax ? K - 1 : kmax] : 64;
+    const int lK = K < nL ? lKs : 64;
     const int cut = lK < rK ? lK : rK;
     wave_lds_sync();
     first = part && cut <= nth ? cut : first;
@@ -259,12 +295,14 @@ __device__ inline void seg2_nth_slots(int n, int nth, const Seg &sg, const SegSc
   double *sl = ss.slik + sb;
   uint32_t *sm = ss.smeta + sb;
   int *lp = ss.lpos + sb, *rp = ss.rpos + sb;
-  int *jl0 = ss.junk + lane, *jl1 = ss.junk + 64 + lane, *jr0 = ss.junk + 128 + lane, *jr1 = ss.junk + 192 + lane;
+  int *jk = ss.junk + lane;  // never read: one slot per lane serves all four writes
   const int kmax = 2 * W - 1;
   const int p0 = k, p1 = k + W;  // this lane's positions
+  const uint64_t b_act = wave_ballot(act);
+  if (k == 0) rp[0] = 64;  // r_{-1}: stays for the whole call (stops go to rp[1 ..])
   while (true) {
     const bool part = act && last - first > 3 && depth > 0;
-    if (!wave_ballot(part)) break;
+    if (!(b_act & wave_ballot(last - first > 3) & wave_ballot(depth > 0))) break;
     depth -= part ? 1 : 0;
     // std::__move_median_to_first(first, first+1, mid, last-1) (stl_algo.h:79-102)
     const int a = first + 1, b = first + ((last - first) >> 1), c = last > 0 ? last - 1 : 0;
@@ -273,7 +311,8 @@ __device__ inline void seg2_nth_slots(int n, int nth, const Seg &sg, const SegSc
     const uint32_t m0 = sm[p0], m1 = sm[p1];
     const int idx = (va > vb ? 4 : 0) | (vb > vc ? 2 : 0) | (va > vc ? 1 : 0);
     const int w = (22561 >> (2 * idx)) & 3;
-    const int r = w == 0 ? a : (w == 1 ? b : c);
+    // where the median comes from; `first` (the identity) in a segment that sits this round out
+    const int r = !part ? first : (w == 0 ? a : (w == 1 ? b : c));
     const double pivot = w == 0 ? va : (w == 1 ? vb : vc);
     // the value each position holds once the median is at first
     const double pv0 = p0 == first ? pivot : (p0 == r ? vf : v0);
@@ -281,42 +320,41 @@ __device__ inline void seg2_nth_slots(int n, int nth, const Seg &sg, const SegSc
     // stop masks over positions: ballot bits of element 0 at [0, W), element 1 at [W, 2W)
     const uint32_t le = seg_bits(wave_ballot(!(pv0 > pivot)), sg) | seg_bits(wave_ballot(!(pv1 > pivot)), sg) << W;
     const uint32_t ge = seg_bits(wave_ballot(!(pivot > pv0)), sg) | seg_bits(wave_ballot(!(pivot > pv1)), sg) << W;
-    const uint32_t below_last = last >= 32 ? ~0u : ((1u << last) - 1u);
-    const uint32_t inR = part ? below_last & ~((1u << first) - 1u) : 0u;  // [first, last)
-    const uint32_t inL = inR & ~(1u << first);                             // (first, last)
-    const uint32_t Lw = le & inL, Rw = ge & inR;
-    const int nL = __popc(Lw), nR = __popc(Rw);
+    const uint32_t in = part ? (2u << c) - (2u << first) : 0u;  // (first, last): first < c = last - 1 <= 31
+    const uint32_t Lw = le & in, Rw = ge & in;                  // Rw: the right stops but `first`
+    const int nL = __popc(Lw);
     // each element's position once the median is at first
-    const int x0 = !part ? p0 : (p0 == first ? r : (p0 == r ? first : p0));
-    const int x1 = !part ? p1 : (p1 == first ? r : (p1 == r ? first : p1));
-    const bool isL0 = part && ((Lw >> x0) & 1u), isR0 = part && ((Rw >> x0) & 1u);
-    const bool isL1 = part && ((Lw >> x1) & 1u), isR1 = part && ((Rw >> x1) & 1u);
-    const uint32_t xb0 = (1u << x0) - 1u, xb1 = (1u << x1) - 1u;
-    const int kL0 = __popc(Lw & xb0), kL1 = __popc(Lw & xb1);
-    const int kR0 = nR - 1 - __popc(Rw & xb0), kR1 = nR - 1 - __popc(Rw & xb1);
-    *(isL0 ? lp + kL0 : jl0) = x0;
-    *(isL1 ? lp + kL1 : jl1) = x1;
-    *(isR0 ? rp + kR0 : jr0) = x0;
-    *(isR1 ? rp + kR1 : jr1) = x1;
+    const int x0 = p0 == first ? r : (p0 == r ? first : p0);
+    const int x1 = p1 == first ? r : (p1 == r ? first : p1);
+    const bool isL0 = (Lw >> x0) & 1u, isR0 = (Rw >> x0) & 1u;
+    const bool isL1 = (Lw >> x1) & 1u, isR1 = (Rw >> x1) & 1u;
+    // left stops below and right stops above each element: its pair index as a
+    // stop of either kind, and the swap decision (header comment)
+    const int kL0 = __popc(Lw & ((1u << x0) - 1u)), kL1 = __popc(Lw & ((1u << x1) - 1u));
+    const int kR0 = __popc((Rw >> 1) >> x0), kR1 = __popc((Rw >> 1) >> x1);
+    const uint64_t b_lsw0 = wave_ballot(isL0) & wave_ballot(kR0 > kL0);
+    const uint64_t b_lsw1 = wave_ballot(isL1) & wave_ballot(kR1 > kL1);
+    const bool lsw0 = isL0 && kR0 > kL0, lsw1 = isL1 && kR1 > kL1;
+    const bool rsw0 = isR0 && kL0 > kR0, rsw1 = isR1 && kL1 > kR1;
+    const int K = __popc(seg_bits(b_lsw0, sg) | seg_bits(b_lsw1, sg) << W);
+    *(isL0 ? lp + kL0 : jk) = x0;
+    *(isL1 ? lp + kL1 : jk) = x1;
+    *(isR0 ? rp + 1 + kR0 : jk) = x0;
+    *(isR1 ? rp + 1 + kR1 : jk) = x1;
     wave_lds_sync();
-    const int qR0 = rp[kL0 < kmax ? kL0 : kmax], qR1 = rp[kL1 < kmax ? kL1 : kmax];
-    const int qL0 = lp[kR0 < 0 ? 0 : (kR0 < kmax ? kR0 : kmax)];
-    const int qL1 = lp[kR1 < 0 ? 0 : (kR1 < kmax ? kR1 : kmax)];
-    const bool lsw0 = isL0 && kL0 < nR && x0 < qR0, lsw1 = isL1 && kL1 < nR && x1 < qR1;
-    const bool rsw0 = isR0 && kR0 < nL && qL0 < x0, rsw1 = isR1 && kR1 < nL && qL1 < x1;
+    // one batch: the partners and the cut = min(l_K, r_{K-1}).  Every index
+    // is inside the segment's 2W slots (kL < x, kR and K < 2W); a lane that
+    // does not swap reads a slot it does not use.
+    int qR0 = rp[1 + kL0], qR1 = rp[1 + kL1];
+    int qL0 = lp[kR0], qL1 = lp[kR1];
+    int lKs = lp[K], rK = rp[K];
+    lds_batch(qR0, qR1, qL0, qL1, lKs, rK);
     const int d0 = lsw0 ? qR0 : (rsw0 ? qL0 : x0), d1 = lsw1 ? qR1 : (rsw1 ? qL1 : x1);
     sl[d0] = v0;
     sm[d0] = m0;
     sl[d1] = v1;
     sm[d1] = m1;
-    // cut = min(l_K, r_{K-1}) (see seg_nth_slots), K = the number of swapping
-    // pairs: the swaps are a prefix of the stop pairs, and the stops' positions
-    // are still in lp / rp (one popcount and two LDS reads instead of four
-    // stop ballots re-based to positions: 3.7-4.5 % less time per add,
-    // coop_bench mode 8 vs 5, profiles/r04/coop/)
-    const int K = __popcll(wave_ballot(lsw0) & sg.mask) + __popcll(wave_ballot(lsw1) & sg.mask);
-    const int lK = K < nL ? lp[K < kmax ? K : kmax] : 64;
-    const int rK = K > 0 ? rp[K - 1 < kmax ? K - 1 : kmax] : 64;
+    const int lK = K < nL ? lKs : 64;
     const int cut = lK < rK ? lK : rK;
     wave_lds_sync();
     first = part && cut <= nth ? cut : first;

@@ -18,6 +18,8 @@
 //   mode 7: as mode 5 with lane-major slots (seg2m_nth_slots)
 //   mode 9: as mode 5 with S = 10 fixed at compile time (the product's
 //   estep_values<..., PAIR, 10>: the helpers are inlined, so S folds)
+//   mode 10 / 11: as modes 5 / 9 with the partition of before the swap rule
+//   (seg2_nth_slots_paired: partner test by position, cut in a third LDS trip)
 #include <hip/hip_runtime.h>
 
 #include <cstdio>
@@ -455,6 +457,121 @@ __device__ inline void seg2m_nth_slots(int n, int nth, const Seg &sg, double *sl
   }
 }
 
+// seg2_nth_slots as it was before the swap decisions came from the stop
+// counts (modes 10 / 11): every stop reads its partner's position and swaps
+// iff the partner lies beyond it, K is a ballot of that test, and the cut is a
+// third LDS round trip behind it; clamped indices, four junk slots per lane.
+// Same permutation as seg2_nth_slots — kept to measure one against the other.
+__device__ inline void seg2_nth_slots_paired(int n, int nth, const Seg &sg, const SegScratch &ss) {
+  const int lane = (int)(threadIdx.x & 63);
+  const int W = sg.sw, k = sg.k;
+  int first = 0, last = n, depth = n > 0 ? lg2_floor(n) * 2 : 0;
+  const bool act = n > 0 && nth != n && sg.mask != 0ull;
+  const int sb = sg.g * 2 * W;  // the segment's first slot
+  double *sl = ss.slik + sb;
+  uint32_t *sm = ss.smeta + sb;
+  int *lp = ss.lpos + sb, *rp = ss.rpos + sb;
+  int *jl0 = ss.junk + lane, *jl1 = ss.junk + 64 + lane, *jr0 = ss.junk + 128 + lane, *jr1 = ss.junk + 192 + lane;
+  const int kmax = 2 * W - 1;
+  const int p0 = k, p1 = k + W;  // this lane's positions
+  while (true) {
+    const bool part = act && last - first > 3 && depth > 0;
+    if (!wave_ballot(part)) break;
+    depth -= part ? 1 : 0;
+    const int a = first + 1, b = first + ((last - first) >> 1), c = last > 0 ? last - 1 : 0;
+    const double va = sl[a], vb = sl[b], vc = sl[c], vf = sl[first];
+    const double v0 = sl[p0], v1 = sl[p1];
+    const uint32_t m0 = sm[p0], m1 = sm[p1];
+    const int idx = (va > vb ? 4 : 0) | (vb > vc ? 2 : 0) | (va > vc ? 1 : 0);
+    const int w = (22561 >> (2 * idx)) & 3;
+    const int r = w == 0 ? a : (w == 1 ? b : c);
+    const double pivot = w == 0 ? va : (w == 1 ? vb : vc);
+    const double pv0 = p0 == first ? pivot : (p0 == r ? vf : v0);
+    const double pv1 = p1 == first ? pivot : (p1 == r ? vf : v1);
+    const uint32_t le = seg_bits(wave_ballot(!(pv0 > pivot)), sg) | seg_bits(wave_ballot(!(pv1 > pivot)), sg) << W;
+    const uint32_t ge = seg_bits(wave_ballot(!(pivot > pv0)), sg) | seg_bits(wave_ballot(!(pivot > pv1)), sg) << W;
+    const uint32_t below_last = last >= 32 ? ~0u : ((1u << last) - 1u);
+    const uint32_t inR = part ? below_last & ~((1u << first) - 1u) : 0u;  // [first, last)
+    const uint32_t inL = inR & ~(1u << first);                             // (first, last)
+    const uint32_t Lw = le & inL, Rw = ge & inR;
+    const int nL = __popc(Lw), nR = __popc(Rw);
+    const int x0 = !part ? p0 : (p0 == first ? r : (p0 == r ? first : p0));
+    const int x1 = !part ? p1 : (p1 == first ? r : (p1 == r ? first : p1));
+    const bool isL0 = part && ((Lw >> x0) & 1u), isR0 = part && ((Rw >> x0) & 1u);
+    const bool isL1 = part && ((Lw >> x1) & 1u), isR1 = part && ((Rw >> x1) & 1u);
+    const uint32_t xb0 = (1u << x0) - 1u, xb1 = (1u << x1) - 1u;
+    const int kL0 = __popc(Lw & xb0), kL1 = __popc(Lw & xb1);
+    const int kR0 = nR - 1 - __popc(Rw & xb0), kR1 = nR - 1 - __popc(Rw & xb1);
+    *(isL0 ? lp + kL0 : jl0) = x0;
+    *(isL1 ? lp + kL1 : jl1) = x1;
+    *(isR0 ? rp + kR0 : jr0) = x0;
+    *(isR1 ? rp + kR1 : jr1) = x1;
+    wave_lds_sync();
+    const int qR0 = rp[kL0 < kmax ? kL0 : kmax], qR1 = rp[kL1 < kmax ? kL1 : kmax];
+    const int qL0 = lp[kR0 < 0 ? 0 : (kR0 < kmax ? kR0 : kmax)];
+    const int qL1 = lp[kR1 < 0 ? 0 : (kR1 < kmax ? kR1 : kmax)];
+    const bool lsw0 = isL0 && kL0 < nR && x0 < qR0, lsw1 = isL1 && kL1 < nR && x1 < qR1;
+    const bool rsw0 = isR0 && kR0 < nL && qL0 < x0, rsw1 = isR1 && kR1 < nL && qL1 < x1;
+    const int d0 = lsw0 ? qR0 : (rsw0 ? qL0 : x0), d1 = lsw1 ? qR1 : (rsw1 ? qL1 : x1);
+    sl[d0] = v0;
+    sm[d0] = m0;
+    sl[d1] = v1;
+    sm[d1] = m1;
+    const int K = __popcll(wave_ballot(lsw0) & sg.mask) + __popcll(wave_ballot(lsw1) & sg.mask);
+    const int lK = K < nL ? lp[K < kmax ? K : kmax] : 64;
+    const int rK = K > 0 ? rp[K - 1 < kmax ? K - 1 : kmax] : 64;
+    const int cut = lK < rK ? lK : rK;
+    wave_lds_sync();
+    first = part && cut <= nth ? cut : first;
+    last = part && cut > nth ? cut : last;
+  }
+  const bool heap = act && last - first > 3;
+  if (wave_ballot(heap)) {
+    if (heap && k == 0) {
+      const LinkList wl{sl, sm, 1};
+      heap_select(wl, first, nth + 1, last);
+      wl.swap(first, nth);
+    }
+    wave_lds_sync();
+  }
+  const bool ins = act && !heap && last - first > 1;
+  if (wave_ballot(ins)) {
+    const int len = last - first;
+    const int f0 = first < kmax ? first : kmax;
+    const int f1 = first + 1 < kmax ? first + 1 : kmax, f2 = first + 2 < kmax ? first + 2 : kmax;
+    double y0 = sl[f0], y1 = sl[f1], y2 = sl[f2];
+    uint32_t t0 = sm[f0], t1 = sm[f1], t2 = sm[f2];
+    if (y1 > y0) {
+      const double t = y1; y1 = y0; y0 = t;
+      const uint32_t u = t1; t1 = t0; t0 = u;
+    }
+    if (len > 2) {
+      if (y2 > y0) {
+        const double t = y2; const uint32_t u = t2;
+        y2 = y1; t2 = t1; y1 = y0; t1 = t0; y0 = t; t0 = u;
+      } else if (y2 > y1) {
+        const double t = y2; const uint32_t u = t2;
+        y2 = y1; t2 = t1; y1 = t; t1 = u;
+      }
+    }
+    const int j0 = p0 - first, j1 = p1 - first;
+    const bool mine0 = ins && (j0 == 0 || j0 == 1 || (j0 == 2 && len > 2));
+    const bool mine1 = ins && (j1 == 0 || j1 == 1 || (j1 == 2 && len > 2));
+    const double z0 = j0 == 0 ? y0 : (j0 == 1 ? y1 : y2), z1 = j1 == 0 ? y0 : (j1 == 1 ? y1 : y2);
+    const uint32_t u0 = j0 == 0 ? t0 : (j0 == 1 ? t1 : t2), u1 = j1 == 0 ? t0 : (j1 == 1 ? t1 : t2);
+    wave_lds_sync();
+    if (mine0) {
+      sl[p0] = z0;
+      sm[p0] = u0;
+    }
+    if (mine1) {
+      sl[p1] = z1;
+      sm[p1] = u1;
+    }
+    wave_lds_sync();
+  }
+}
+
 // mode 7: two links per lane, lane-major slots (seg2m_nth_slots)
 __global__ __launch_bounds__(64) void bench_seg2m(int S, int adds, double *out) {
   extern __shared__ unsigned char sm[];
@@ -592,8 +709,10 @@ __global__ __launch_bounds__(64) void bench_seg2(int S, int adds, double *out) {
 }
 
 // mode 5: two elements per lane, S lanes per list (seg2_nth_slots); mode 8:
-// the same (the round-4 A/B of the cut from the swap count, now the only one)
-template <bool KCUT, int SC = 0>
+// the same (the round-4 A/B of the cut from the swap count, now the only one);
+// PAIRED (modes 10 / 11): the partition before the swap decisions came from
+// the stop counts (seg2_nth_slots_paired)
+template <bool PAIRED, int SC = 0>
 __global__ __launch_bounds__(64) void bench_seg2e(int S_, int adds, double *out) {
   extern __shared__ unsigned char sm[];
   const int S = SC > 0 ? SC : S_;
@@ -617,8 +736,8 @@ __global__ __launch_bounds__(64) void bench_seg2e(int S_, int adds, double *out)
       ss.smeta[sb + S + sg.k] = 64u * r + sg.k;
     }
     wave_lds_sync();
-    (void)KCUT;
-    seg2_nth_slots(in ? 2 * S : 0, S - 1, sg, ss);
+    if constexpr (PAIRED) seg2_nth_slots_paired(in ? 2 * S : 0, S - 1, sg, ss);
+    else seg2_nth_slots(in ? 2 * S : 0, S - 1, sg, ss);
   }
   double acc = 0.0;
   if (in) acc = ss.slik[sb + sg.k] * (double)(ss.smeta[sb + sg.k] % 97);
@@ -657,19 +776,20 @@ int main(int argc, char **argv) {
   // mode 2/3 with wpc / (32 / S) process the same lists.
   const int G = 64 / (2 * S);
   const int lists = mode == 2 || mode == 3 ? cu * wpc * 64 : cu * wpc * G;
-  if (mode < 0 || mode == 1 || mode > 9 || (mode == 9 && S != 10)) return 1;
+  if (mode < 0 || mode == 1 || mode > 11 || ((mode == 9 || mode == 11) && S != 10)) return 1;
+  const bool pairm = mode == 5 || mode == 7 || mode == 8 || mode == 9 || mode == 10 || mode == 11;
   const int G5 = 64 / S, G6 = 64 / ((2 * S + 3) / 4);
   int grid = mode == 0 ? cu * wpc
                        : (mode == 4 ? cu * wpc / 2
-                                    : (mode == 5 || mode == 7 || mode == 8 || mode == 9 ? (lists + G5 - 1) / G5
+                                    : (pairm ? (lists + G5 - 1) / G5
                                                               : (mode == 6 ? (lists + G6 - 1) / G6 : (lists + 63) / 64)));
-  size_t lds = mode == 2 || mode == 3 ? (size_t)2 * S * 64 * 12 : (mode == 4 ? 4096 : (mode == 5 || mode == 7 || mode == 8 || mode == 9 ? 4608 : (mode == 6 ? 8448 : 2048)));
+  size_t lds = mode == 2 || mode == 3 ? (size_t)2 * S * 64 * 12 : (mode == 4 ? 4096 : (pairm ? 4608 : (mode == 6 ? 8448 : 2048)));
   void (*kern)(int, int, double *) =
       mode == 0 ? bench_seg
                 : (mode == 2 ? bench_lane<false>
                              : (mode == 3 ? bench_lane<true>
                                           : (mode == 4 ? bench_seg2
-                                                       : (mode == 5 ? bench_seg2e<false> : (mode == 8 ? bench_seg2e<true> : (mode == 9 ? bench_seg2e<false, 10> : (mode == 6 ? bench_seg4e : bench_seg2m)))))));
+                                                       : (mode == 5 || mode == 8 ? bench_seg2e<false> : (mode == 9 ? bench_seg2e<false, 10> : (mode == 10 ? bench_seg2e<true> : (mode == 11 ? bench_seg2e<true, 10> : (mode == 6 ? bench_seg4e : bench_seg2m))))))));
   if (lds > 65536) (void)hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
   double *out;
   (void)hipMalloc(&out, grid * sizeof(double));
