@@ -92,6 +92,9 @@ _SIGS = [
     ("hmc_set_pair_tuning", _i, [_vp, _i, _i]),
     ("hmc_posterior_draws", _i, [_vp, C.c_int64, _P(C.c_int32), _i, _u64, _P(C.c_int32), _P(_d), _P(C.c_int32)]),
     ("hmc_last_draw_stats", _i, [_vp, _P(_d), _P(_d), _P(_d), _P(_i), _P(_i)]),
+    ("hmc_set_posterior_range", _i, [_vp, _i]),
+    ("hmc_genotype_likelihoods", _i, [_vp, C.c_int64, _P(C.c_int32), _P(_d), _P(C.c_int32), _P(C.c_int32)]),
+    ("hmc_last_likelihood_stats", _i, [_vp, _P(_d), _P(_d), _P(_i)]),
     ("hmc_set_draw_tuning", _i, [_vp, _i, _i]),
     ("hmc_write_posterior_draws", _i, [_vp, _cp, _i, _u64]),
     ("hmc_test_draw_uniform", _d, [_u64, C.c_int32, C.c_int32, C.c_int32]),

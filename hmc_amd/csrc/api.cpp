@@ -996,6 +996,28 @@ int hmc_posterior_draws(hmc_ctx *h, int64_t n, const int32_t *indiv, int draws, 
   return c.posterior_draws(n, indiv, draws, seed, hap, prob, status);
 }
 
+int hmc_set_posterior_range(hmc_ctx *h, int extended) {
+  if (!h) return HMC_EARG;
+  if (extended != 0 && extended != 1) return h->c.fail(HMC_EARG, "posterior range: %d is neither 0 (regular) nor 1 (extended)", extended);
+  h->c.xp_extended = extended != 0;
+  return HMC_OK;
+}
+
+int hmc_genotype_likelihoods(hmc_ctx *h, int64_t n, const int32_t *indiv, double *mantissa, int32_t *exponent, int32_t *status) {
+  if (!h) return HMC_EARG;
+  Ctx &c = h->c;
+  if (!c.have_panel) return c.fail(HMC_EARG, "no panel loaded");
+  return c.genotype_likelihoods(n, indiv, mantissa, exponent, status);
+}
+
+int hmc_last_likelihood_stats(const hmc_ctx *h, double *structure_ms, double *fb_ms, int *groups) {
+  if (!h) return HMC_EARG;
+  if (structure_ms) *structure_ms = h->c.lk_ms_struct;
+  if (fb_ms) *fb_ms = h->c.lk_ms_fb;
+  if (groups) *groups = h->c.lk_groups;
+  return HMC_OK;
+}
+
 int hmc_last_draw_stats(const hmc_ctx *h, double *structure_ms, double *fb_ms, double *draw_ms, int *groups, int *n_pruned) {
   if (!h) return HMC_EARG;
   if (structure_ms) *structure_ms = h->c.dr_ms_struct;

@@ -809,8 +809,24 @@ struct Ctx {
   void site_list(SiteList &sl) const;
   int site_group(const ExactArgs &x, int k, int dev_cu);
   // what the exact group runs after exact_fb in place of the trie walk
-  enum XpMode { XP_OFF = 0, XP_GENOTYPE = 1, XP_SWITCH = 2, XP_PAIR = 3, XP_DRAW = 4 };
+  enum XpMode { XP_OFF = 0, XP_GENOTYPE = 1, XP_SWITCH = 2, XP_PAIR = 3, XP_DRAW = 4, XP_LIK = 5 };
   XpMode xp_mode = XP_OFF;
+  // Extended range (hmc_set_posterior_range): the four posterior calls run
+  // exact_fb's scaled pass (ExactArgs::extended) and divide by its own total,
+  // so no individual is given up for underflow: no pruned re-run, no status 2.
+  bool xp_extended = false;
+  DevBuf<double> d_xtot;        // [shard] the scaled total of the final record
+  DevBuf<int32_t> d_xtot_exp;   // [shard] its exponent E_L
+  // P(genotype) as mantissa x 2^exponent from the scaled forward pass
+  // (hmc_genotype_likelihoods; XP_LIK: nothing runs after exact_fb), always
+  // extended.  Rows are the caller's; indiv NULL: the whole shard.
+  int genotype_likelihoods(int64_t n, const int32_t *indiv, double *mantissa, int32_t *exponent, int32_t *status);
+  struct LikCall {  // the running call, per individual of the shard
+    std::vector<double> mantissa;
+    std::vector<int32_t> exponent, status;
+  } lk;
+  double lk_ms_struct = 0, lk_ms_fb = 0;  // of the last call
+  int lk_groups = 0;
   // The part the two posterior calls share: every individual of the shard
   // through estep_split(order, true) with xp_mode = mode, and whatever that
   // pass shares with the E-step saved before and put back after.

@@ -200,7 +200,14 @@ int Ctx::exact_group(const int32_t *ids, int k, const std::function<int(std::vec
   x.head_al = d_head_al.p;
   x.acc_freq = d_xacc.p;
   x.acc_prefix = d_xacc.p + xacc_nc;
-  x.forward_only = xp_mode == XP_DRAW && dr_forward_only;
+  x.forward_only = (xp_mode == XP_DRAW && dr_forward_only) || xp_mode == XP_LIK;
+  // extended range: the posterior calls when asked for, the likelihoods always, the exact M-step never
+  x.extended = xp_mode == XP_LIK || (xp_mode != XP_OFF && xp_extended);
+  if (x.extended) {
+    if ((e = d_xtot.ensure(nloc())) || (e = d_xtot_exp.ensure(nloc()))) return hipfail(e, "exact_fb");
+    x.xtot = d_xtot.p;
+    x.xtot_exp = d_xtot_exp.p;
+  }
   if (xc_reuse) {  // a later round over the same group: records and fwd/bwd sums are still in place
     x.fmax = xc_fmax;
     return exact_walk_group(x, k, dev_cu);
@@ -254,6 +261,22 @@ int Ctx::exact_group(const int32_t *ids, int k, const std::function<int(std::vec
   if (xp_mode == XP_SWITCH) return switch_group(x, ids, fm, k, dev_cu);
   if (xp_mode == XP_PAIR) return pair_group(x, ids, fm, k, dev_cu);
   if (xp_mode == XP_DRAW) return draw_group(x, ids, k, dev_cu);
+  if (xp_mode == XP_LIK) {  // the scaled totals of the group's individuals: nothing runs after exact_fb
+    std::vector<double> tot(n);
+    std::vector<int32_t> ex(n);
+    if ((e = hipMemcpyAsync(tot.data(), d_xtot.p, (size_t)n * 8, hipMemcpyDeviceToHost, st)) ||
+        (e = hipMemcpyAsync(ex.data(), d_xtot_exp.p, (size_t)n * 4, hipMemcpyDeviceToHost, st)) || (e = sync_st()))
+      return hipfail(e, "genotype likelihoods");
+    for (int q = 0; q < k; ++q) {
+      const int bi = ids[q];
+      if (xs[bi] != EST_OK || !(tot[bi] > 0.0) || std::isinf(tot[bi])) continue;  // status 1, (0.0, 0)
+      int fe = 0;
+      lk.mantissa[bi] = std::frexp(tot[bi], &fe);  // P(genotype) = tot 2^-E_L
+      lk.exponent[bi] = fe - ex[bi];
+      lk.status[bi] = 0;
+    }
+    return HMC_OK;
+  }
   return exact_walk_group(x, k, dev_cu);
 }
 
@@ -728,6 +751,51 @@ int Ctx::posterior_draws(int64_t n, const int32_t *indiv, int draws, uint64_t se
         for (int side = 0; side < 2; ++side)
           for (int l = 0; l < L; ++l)
             hap[(((size_t)q * draws + d) * 2 + side) * L + l] = pan.symbol(l, pan.idx[((size_t)(i0 + i) * 2 + side) * L + l]);
+  }
+  return HMC_OK;
+}
+
+int Ctx::genotype_likelihoods(int64_t n, const int32_t *indiv, double *mantissa, int32_t *exponent, int32_t *status) {
+  if (!have_estep) return fail(HMC_EARG, "genotype likelihoods need an E-step first (hmc_resolve_all)");
+  if (estep_gen != model_gen)
+    return fail(HMC_EARG, "genotype likelihoods: the model changed since the last E-step (hmc_resolve_all again)");
+  if (pan.amax > 44) return fail(HMC_EUNSUPPORTED, "genotype likelihoods with more than 44 alleles per locus");
+  const int nl = nloc();
+  if (!indiv) n = nl;
+  if (n < 0) return fail(HMC_EARG, "genotype likelihoods: n = %lld is negative", (long long)n);
+  for (int64_t q = 0; indiv && q < n; ++q)
+    if (indiv[q] < i0 || indiv[q] >= i1)
+      return fail(HMC_EARG, "genotype likelihoods: entry %lld: individual %d is outside this rank's shard [%d, %d)",
+                  (long long)q, indiv[q], i0, i1);
+  lk_ms_struct = lk_ms_fb = 0;
+  lk_groups = 0;
+  if (n == 0) return HMC_OK;
+  auto local = [&](int64_t q) { return indiv ? indiv[q] - i0 : (int)q; };
+  lk.mantissa.assign(nl, 0.0);
+  lk.exponent.assign(nl, 0);
+  lk.status.assign(nl, 1);
+  hipError_t er;
+  if ((er = d_xstatus.ensure(nl)) || (er = d_xre.ensure(nl)) || (er = d_xfmax.ensure(nl))) return hipfail(er, "genotype likelihoods");
+  // the pass counts in the genotype posteriors' fields: theirs are put back
+  const double g_struct = xp_ms_struct, g_fb = xp_ms_fb, g_sites = xp_ms_sites;
+  const int g_groups = xp_groups, g_pruned = xp_pruned;
+  std::vector<char> asked(nl, 0);  // the passes run over the individuals asked for, not the whole shard
+  for (int64_t q = 0; q < n; ++q) asked[local(q)] = 1;
+  const int rc = xp_pass(XP_LIK, "genotype likelihoods", &asked);
+  lk_ms_struct = xp_ms_struct;
+  lk_ms_fb = xp_ms_fb;
+  lk_groups = xp_groups;
+  xp_ms_struct = g_struct;
+  xp_ms_fb = g_fb;
+  xp_ms_sites = g_sites;
+  xp_groups = g_groups;
+  xp_pruned = g_pruned;
+  if (rc) return rc;
+  for (int64_t q = 0; q < n; ++q) {
+    const int i = local(q);
+    if (mantissa) mantissa[q] = lk.mantissa[i];
+    if (exponent) exponent[q] = lk.exponent[i];
+    if (status) status[q] = lk.status[i];
   }
   return HMC_OK;
 }

@@ -84,9 +84,36 @@ struct RecView {  // one locus record of the structure pass
 
 }  // namespace
 
+// Extended range: the values v[0, F) of one record (each thread has written
+// the entries tid, tid + NT, ... and passes their maximum) times 2^k with k
+// chosen so that the record's maximum lands in [0.5, 1): ldexp, so exact unless
+// an entry is more than 2^1021 below the maximum.  A maximum is order-free, so
+// any reduction gives the same k.  Returns k (block-uniform); 0 for a record of
+// zeros.  Ends on a barrier: the scaled values are visible to the block.
+__device__ inline int rescale_record(double *v, int F, double m) {
+  __shared__ double wmax[16];
+  const int tid = threadIdx.x, NT = blockDim.x, nw = NT / WAVE;
+#pragma unroll
+  for (int o = WAVE / 2; o > 0; o >>= 1) m = fmax(m, __shfl_xor(m, o));
+  if ((tid & (WAVE - 1)) == 0) wmax[tid / WAVE] = m;
+  __syncthreads();
+  m = wmax[0];
+  for (int w = 1; w < nw; ++w) m = fmax(m, wmax[w]);
+  const int k = m > 0.0 && !isinf(m) ? -1 - ilogb(m) : 0;
+  if (k != 0)
+    for (int t = tid; t < F; t += NT) v[t] = ldexp(v[t], k);
+  __syncthreads();
+  return k;
+}
+
 // Forward and backward likelihoods of every state of every locus (block per individual).
 // BACKWARD = false (ExactArgs::forward_only, the posterior draws) stops after the forward pass.
-template <bool BACKWARD>
+// EXT = true (ExactArgs::extended): every record rescaled by an exact power of
+// two (rescale_record), the cumulative exponents in the record's spare words,
+// the scaled total of the final record and its exponent per individual; no
+// underflow flag, so no pruned re-run.  EXT = false is the raw-double pass the
+// exact M-step (exact_walk) reads.
+template <bool BACKWARD, bool EXT>
 __global__ __launch_bounds__(256) void exact_fb(ExactArgs a) {
   const int tid = threadIdx.x, NT = blockDim.x;
   const int L = a.L, hl = a.head_len;
@@ -108,12 +135,19 @@ __global__ __launch_bounds__(256) void exact_fb(ExactArgs a) {
     if (tid == 0) flag = 0;
     __syncthreads();
     // forward (HaploPair.cpp:27-32 head, :42 / :66 extension and add)
+    int ex = 0;  // EXT: the cumulative forward exponent E_j (block-uniform)
     {
       const RecView R(a.rec + roff[hl], true);
       double *fw = (double *)(a.x + xo[hl]);
+      double m = 0.0;
       for (int t = tid; t < R.F; t += NT) {
         const bool homo = (R.hdr[t] >> 24) & 1u;
         fw[t] = homo ? R.tpv[t] : R.tpv[t] * 2.0;
+        if constexpr (EXT) m = fmax(m, fw[t]);
+      }
+      if constexpr (EXT) {
+        ex += rescale_record(fw, R.F, m);
+        if (tid == 0) ((int32_t *)(fw + 2 * (size_t)R.F))[0] = ex;
       }
     }
     __syncthreads();
@@ -121,6 +155,7 @@ __global__ __launch_bounds__(256) void exact_fb(ExactArgs a) {
       const RecView R(a.rec + roff[j], false);
       const double *fp = (const double *)(a.x + xo[j - 1]);
       double *fw = (double *)(a.x + xo[j]);
+      double m = 0.0;
       for (int t = tid; t < R.F; t += NT) {
         const double tpv = R.tpv[t];
         double f = 0.0;
@@ -129,24 +164,47 @@ __global__ __launch_bounds__(256) void exact_fb(ExactArgs a) {
           f = r == R.cb[t] ? v : f + v;
         }
         fw[t] = f;
-        if (!(f > 0.0) && j < L && !pruned) flag = 1;  // extend() would skip this pair (HaploBuilder.cpp:237)
+        if constexpr (EXT) m = fmax(m, f);
+        else if (!(f > 0.0) && j < L && !pruned) flag = 1;  // extend() would skip this pair (HaploBuilder.cpp:237)
       }
-      __syncthreads();
+      if constexpr (EXT) {
+        ex += rescale_record(fw, R.F, m);
+        if (tid == 0) ((int32_t *)(fw + 2 * (size_t)R.F))[0] = ex;
+      } else {
+        __syncthreads();
+      }
+    }
+    if constexpr (EXT) {
+      // the divisor: the final record's scaled values summed as the value pass sums
+      // its total, sequentially in state order from 0.0, with the exponent E_L
+      if (tid == 0) {
+        const int F = (int)a.rec[roff[L]];
+        const double *fw = (const double *)(a.x + xo[L]);
+        double tot = 0.0;
+        for (int t = 0; t < F; ++t) tot += fw[t];
+        a.xtot[bi] = tot;
+        a.xtot_exp[bi] = ex;
+      }
     }
     // every thread reads the flag before any thread can reset it for the next
     // individual (the reset sits before the barrier at the top of the loop)
-    const bool underflow = flag != 0;
-    __syncthreads();
-    if (underflow) {
-      if (tid == 0) a.status[bi] = EST_NEEDS_EXACT;
-      continue;
+    if constexpr (!EXT) {
+      const bool underflow = flag != 0;
+      __syncthreads();
+      if (underflow) {
+        if (tid == 0) a.status[bi] = EST_NEEDS_EXACT;
+        continue;
+      }
     }
     if (!BACKWARD) continue;
     // backward: states of m_haplopairs[L] keep m_backward_likelihood = 1.0
+    int gx = 0;  // EXT: the cumulative backward exponent G_j (block-uniform; G_L = 0)
     {
       const RecView R(a.rec + roff[L], L == hl);
       double *bw = (double *)(a.x + xo[L]) + R.F;
       for (int t = tid; t < R.F; t += NT) bw[t] = 1.0;
+      if constexpr (EXT)
+        if (tid == 0) ((int32_t *)(bw + R.F))[1] = 0;
     }
     __syncthreads();
     for (int j = L - 1; j >= hl; --j) {
@@ -154,6 +212,7 @@ __global__ __launch_bounds__(256) void exact_fb(ExactArgs a) {
       const RecView N(a.rec + roff[j + 1], false);     // their forward links
       const double *bn = (const double *)(a.x + xo[j + 1]) + N.F;
       double *bw = (double *)(a.x + xo[j]) + R.F;
+      double m = 0.0;
       for (int s = tid; s < R.F; s += NT) {
         double b = 0.0;
         for (int pass = 0; pass < 2; ++pass) {  // m_forward_links[0], then [1], each in push order
@@ -171,8 +230,14 @@ __global__ __launch_bounds__(256) void exact_fb(ExactArgs a) {
           }
         }
         bw[s] = b;
+        if constexpr (EXT) m = fmax(m, b);
       }
-      __syncthreads();
+      if constexpr (EXT) {
+        gx += rescale_record(bw, R.F, m);
+        if (tid == 0) ((int32_t *)(bw + R.F))[1] = gx;
+      } else {
+        __syncthreads();
+      }
     }
   }
 }
@@ -941,8 +1006,14 @@ size_t exact_walk_scratch_doubles(int max_depth, long long span, int width) {
 
 hipError_t launch_exact_fb(const ExactArgs &a, int grid, hipStream_t st) {
   if (a.n_order <= 0) return hipSuccess;
-  if (a.forward_only) hipLaunchKernelGGL(exact_fb<false>, dim3(grid), dim3(256), 0, st, a);
-  else hipLaunchKernelGGL(exact_fb<true>, dim3(grid), dim3(256), 0, st, a);
+  if (a.extended) {
+    if (!a.xtot || !a.xtot_exp) return hipErrorInvalidValue;
+    if (a.forward_only) hipLaunchKernelGGL((exact_fb<false, true>), dim3(grid), dim3(256), 0, st, a);
+    else hipLaunchKernelGGL((exact_fb<true, true>), dim3(grid), dim3(256), 0, st, a);
+    return hipGetLastError();
+  }
+  if (a.forward_only) hipLaunchKernelGGL((exact_fb<false, false>), dim3(grid), dim3(256), 0, st, a);
+  else hipLaunchKernelGGL((exact_fb<true, false>), dim3(grid), dim3(256), 0, st, a);
   return hipGetLastError();
 }
 
@@ -995,6 +1066,12 @@ hipError_t launch_exact_walk(const ExactArgs &a, int grid, hipStream_t st, int i
 // loci) has lost the bits of its likelihoods — exact_fb and the value pass
 // keep raw doubles — so its rows would not sum to 1: they are zeros with
 // site status 2.
+// EXT (ExactArgs::extended): the x-store holds exact_fb's scaled values; the
+// divisor is the scaled total xtot and the split scaling sc = -ilogb(pg)
+// becomes, per site, the exponent difference E_L - E_j - G_j: the sum over a
+// record of fs bs 2^(E_L - E_j - G_j) is xtot, so nothing overflows.  No
+// status 2; status 1 only when the structure pass found no path or xtot is 0.
+template <bool EXT>
 __global__ __launch_bounds__(1024) void exact_site_posteriors(ExactArgs a, SiteArgs s) {
   const int lane = threadIdx.x & (WAVE - 1), wave = threadIdx.x / WAVE, nw = blockDim.x / WAVE;
   const int L = a.L, hl = a.head_len, NP = s.n_pairs;
@@ -1005,9 +1082,9 @@ __global__ __launch_bounds__(1024) void exact_site_posteriors(ExactArgs a, SiteA
     const unsigned long long s0 = s.site_off[bi], s1 = s.site_off[bi + 1];
     if (s0 == s1) continue;
     const int st0 = a.status[bi];
-    const double pg = a.gprob[bi];
+    const double pg = EXT ? a.xtot[bi] : a.gprob[bi];
     const bool resolved = (st0 == EST_OK || st0 == EST_OK_PRUNED) && pg > 0.0 && !isinf(pg);
-    if (!resolved || pg < SITE_PG_MIN) {  // rows of zeros: unresolved (1), or P(genotype) subnormal (2)
+    if (!resolved || (!EXT && pg < SITE_PG_MIN)) {  // rows of zeros: unresolved (1), or P(genotype) subnormal (2)
       for (unsigned long long i = s0 * NP + threadIdx.x; i < s1 * NP; i += blockDim.x) s.post[i] = 0.0;
       for (unsigned long long i = s0 + threadIdx.x; i < s1; i += blockDim.x) s.site_status[i] = resolved ? 2 : 1;
       continue;
@@ -1019,14 +1096,21 @@ __global__ __launch_bounds__(1024) void exact_site_posteriors(ExactArgs a, SiteA
     // by powers of two that cancel (fwd * bwd <= P(genotype), so nothing
     // overflows).  Exact, so wherever the plain formula stays in the normal
     // range this gives its bits.
-    const int sc = -ilogb(pg), sa = sc / 2, sb = sc - sa;
-    const double pgs = ldexp(pg, sc);
+    int sc = EXT ? 0 : -ilogb(pg), sa = sc / 2, sb = sc - sa;
+    const double pgs = EXT ? pg : ldexp(pg, sc);
+    const int EL = EXT ? a.xtot_exp[bi] : 0;
     for (unsigned long long site = s0; site < s1; ++site) {
       const int k = s.site_locus[site];
       const bool head = k < hl - 1;  // alleles from the head patterns (head_len > 1 only)
       const int j = head ? hl : k + 1;
       const RecView R(a.rec + roff[j], j == hl);
       const double *fw = (const double *)(a.x + xo[j]), *bw = fw + R.F;
+      if constexpr (EXT) {
+        const int32_t *ex = (const int32_t *)(bw + R.F);  // E_j, G_j
+        sc = EL - ex[0] - ex[1];
+        sa = sc / 2;
+        sb = sc - sa;
+      }
       const uint32_t *plo = R.cb + R.F + 1, *phi = plo + R.F;  // head record: the states' two head patterns
       auto bin_of = [&](int t) -> uint32_t {
         if (head) return xpair_index(a.head_al[(size_t)plo[t] * hl + k], a.head_al[(size_t)phi[t] * hl + k]);
@@ -1065,7 +1149,8 @@ hipError_t launch_exact_site_posteriors(const ExactArgs &a, const SiteArgs &s, i
   if (block < WAVE || block > 1024 || block % WAVE || grid < 1 || s.n_pairs != a.width * (a.width + 1) / 2 || !s.site_off ||
       !s.post || !s.site_status)
     return hipErrorInvalidValue;
-  hipLaunchKernelGGL(exact_site_posteriors, dim3(grid), dim3(block), 0, st, a, s);
+  if (a.extended) hipLaunchKernelGGL(exact_site_posteriors<true>, dim3(grid), dim3(block), 0, st, a, s);
+  else hipLaunchKernelGGL(exact_site_posteriors<false>, dim3(grid), dim3(block), 0, st, a, s);
   return hipGetLastError();
 }
 
@@ -1097,6 +1182,11 @@ hipError_t launch_exact_site_posteriors(const ExactArgs &a, const SiteArgs &s, i
 // a site's sums the record's state order, so block size, grid, grouping, shard
 // and tier do not change the bits; no floating-point atomics.
 // Factors are scaled by cancelling powers of two as in exact_site_posteriors.
+// EXT (ExactArgs::extended): as exact_site_posteriors; the label values are
+// anchored from the scaled forward values of their record, so a propagation to
+// record j multiplies them by 2^(E_j - E_(j-1)), the step exact_fb applied to
+// the forward values there (ldexp: exact; g <= fs <= 1, so nothing overflows).
+template <bool EXT>
 __global__ __launch_bounds__(256) void exact_switch_posteriors(ExactArgs a, SwitchArgs s) {
   extern __shared__ double sw_lds[];  // [2 frontiers][tier states][2 labels]
   __shared__ int fmx;
@@ -1108,7 +1198,7 @@ __global__ __launch_bounds__(256) void exact_switch_posteriors(ExactArgs a, Swit
     const unsigned long long s0 = s.site_off[bi], s1 = s.site_off[bi + 1];
     if (s0 == s1) continue;
     const int st0 = a.status[bi];
-    const double pg = a.gprob[bi];
+    const double pg = EXT ? a.xtot[bi] : a.gprob[bi];
     const bool resolved = (st0 == EST_OK || st0 == EST_OK_PRUNED) && pg > 0.0 && !isinf(pg);
     const unsigned long long *roff = a.rec_off + (size_t)bi * (L + 1);
     const unsigned long long *xo = a.x_off + (size_t)bi * (L + 1);
@@ -1127,7 +1217,7 @@ __global__ __launch_bounds__(256) void exact_switch_posteriors(ExactArgs a, Swit
     const bool in_lds = fbig <= s.tier;
     // (a frontier neither store holds cannot occur: the host sizes the scratch from the group's fmax)
     const bool fits = in_lds || (s.scratch && fbig <= s.scratch_states);
-    if (!resolved || pg < SITE_PG_MIN || !fits) {  // rows of zeros: unresolved (1), or P(genotype) subnormal (2)
+    if (!resolved || (!EXT && pg < SITE_PG_MIN) || !fits) {  // rows of zeros: unresolved (1), or P(genotype) subnormal (2)
       for (unsigned long long i = s0 * 2 + tid; i < s1 * 2; i += NT) s.post[i] = 0.0;
       for (unsigned long long i = s0 + tid; i < s1; i += NT) s.site_status[i] = resolved && fits ? 2 : 1;
       continue;
@@ -1135,8 +1225,11 @@ __global__ __launch_bounds__(256) void exact_switch_posteriors(ExactArgs a, Swit
     const size_t cap = in_lds ? (size_t)s.tier : (size_t)s.scratch_states;
     double *cur = in_lds ? sw_lds : s.scratch + (size_t)blockIdx.x * 4 * cap;
     double *prev = cur + 2 * cap;
-    const int sc = -ilogb(pg), sa = sc / 2, sb = sc - sa;
-    const double pgs = ldexp(pg, sc);
+    int sc = EXT ? 0 : -ilogb(pg), sa = sc / 2, sb = sc - sa;
+    const double pgs = EXT ? pg : ldexp(pg, sc);
+    const int EL = EXT ? a.xtot_exp[bi] : 0;
+    // the exponents exact_fb left with record j (EXT): E_j, G_j
+    auto rec_exp = [&](int j) { return (const int32_t *)(a.x + xo[j] + 4ull * a.rec[roff[j]]); };
     // o(t): the side of state t of record j that carries the lower allele of locus k
     // (k < head_len: j is the head record; its hdr word carries locus 0 when head_len is 1)
     auto low_side = [&](const RecView &R, int k, int t) -> int {
@@ -1174,6 +1267,7 @@ __global__ __launch_bounds__(256) void exact_switch_posteriors(ExactArgs a, Swit
         prev = cur;
         cur = x;
         const RecView R(a.rec + roff[j], false);
+        const int step = EXT ? rec_exp(j)[0] - rec_exp(j - 1)[0] : 0;
         for (int t = tid; t < R.F; t += NT) {
           const double tpv = R.tpv[t];
           double n0 = 0.0, n1 = 0.0;
@@ -1185,14 +1279,19 @@ __global__ __launch_bounds__(256) void exact_switch_posteriors(ExactArgs a, Swit
             n0 = r == r0 ? v0 : n0 + v0;
             n1 = r == r0 ? v1 : n1 + v1;
           }
-          cur[2 * t] = n0;
-          cur[2 * t + 1] = n1;
+          cur[2 * t] = EXT ? ldexp(n0, step) : n0;
+          cur[2 * t + 1] = EXT ? ldexp(n1, step) : n1;
         }
         __syncthreads();
       }
       {
         const RecView R(a.rec + roff[j], j == hl);
         const double *bw = (const double *)(a.x + xo[j]) + R.F;
+        if constexpr (EXT) {
+          sc = EL - rec_exp(j)[0] - rec_exp(j)[1];
+          sa = sc / 2;
+          sb = sc - sa;
+        }
         for (int w = wave; w < 2; w += nw) {  // wave-uniform: 0 cis, 1 trans
           double part[1] = {0.0};
           for (int t = lane; t < R.F; t += WAVE)
@@ -1213,7 +1312,8 @@ hipError_t launch_exact_switch_posteriors(const ExactArgs &a, const SwitchArgs &
   if (block < WAVE || block > 256 || block % WAVE || grid < 1 || s.tier < 1 || s.tier > SWITCH_TIER_MAX || !s.site_off ||
       !s.locus_a || !s.locus_b || !s.post || !s.site_status || (s.scratch && s.scratch_states < 1))
     return hipErrorInvalidValue;
-  hipLaunchKernelGGL(exact_switch_posteriors, dim3(grid), dim3(block), (size_t)s.tier * 32, st, a, s);
+  if (a.extended) hipLaunchKernelGGL(exact_switch_posteriors<true>, dim3(grid), dim3(block), (size_t)s.tier * 32, st, a, s);
+  else hipLaunchKernelGGL(exact_switch_posteriors<false>, dim3(grid), dim3(block), (size_t)s.tier * 32, st, a, s);
   return hipGetLastError();
 }
 
@@ -1248,7 +1348,9 @@ hipError_t launch_exact_switch_posteriors(const ExactArgs &a, const SwitchArgs &
 // The frontiers (32 NS bytes per state for the two) live in LDS when the
 // individual's largest record has at most `tier` states, else in the block's
 // slice of an HBM scratch.
-template <int NS>
+// EXT (ExactArgs::extended): as exact_switch_posteriors, every live slot's
+// two sums times the record's forward exponent step.
+template <int NS, bool EXT>
 __global__ __launch_bounds__(256) void exact_pair_posteriors(ExactArgs a, PairArgs s) {
   extern __shared__ __attribute__((aligned(16))) double pr_lds[];  // [2 frontiers][lds_states][NS slots][2 labels]
   __shared__ int fmx;
@@ -1260,7 +1362,7 @@ __global__ __launch_bounds__(256) void exact_pair_posteriors(ExactArgs a, PairAr
     const unsigned long long s0 = s.row_off[bi], s1 = s.row_off[bi + 1];
     if (s0 == s1) continue;
     const int st0 = a.status[bi];
-    const double pg = a.gprob[bi];
+    const double pg = EXT ? a.xtot[bi] : a.gprob[bi];
     const bool resolved = (st0 == EST_OK || st0 == EST_OK_PRUNED) && pg > 0.0 && !isinf(pg);
     const unsigned long long *roff = a.rec_off + (size_t)bi * (L + 1);
     const unsigned long long *xo = a.x_off + (size_t)bi * (L + 1);
@@ -1279,7 +1381,7 @@ __global__ __launch_bounds__(256) void exact_pair_posteriors(ExactArgs a, PairAr
     const bool in_lds = fbig <= s.tier && fbig <= s.lds_states;
     // (a frontier neither store holds cannot occur: the host sizes the scratch from the group's fmax)
     const bool fits = in_lds || (s.scratch && fbig <= s.scratch_states);
-    if (!resolved || pg < SITE_PG_MIN || !fits) {  // rows of zeros: unresolved (1), or P(genotype) subnormal (2)
+    if (!resolved || (!EXT && pg < SITE_PG_MIN) || !fits) {  // rows of zeros: unresolved (1), or P(genotype) subnormal (2)
       for (unsigned long long i = s0 * 2 + tid; i < s1 * 2; i += NT) s.post[i] = 0.0;
       for (unsigned long long i = s0 + tid; i < s1; i += NT) s.row_status[i] = resolved && fits ? 2 : 1;
       continue;
@@ -1287,8 +1389,11 @@ __global__ __launch_bounds__(256) void exact_pair_posteriors(ExactArgs a, PairAr
     const size_t cap = in_lds ? (size_t)s.lds_states : (size_t)s.scratch_states;
     double *cur = in_lds ? pr_lds : s.scratch + (size_t)blockIdx.x * 4 * NS * cap;
     double *prev = cur + 2 * NS * cap;
-    const int sc = -ilogb(pg), sa = sc / 2, sb = sc - sa;
-    const double pgs = ldexp(pg, sc);
+    int sc = EXT ? 0 : -ilogb(pg), sa = sc / 2, sb = sc - sa;
+    const double pgs = EXT ? pg : ldexp(pg, sc);
+    const int EL = EXT ? a.xtot_exp[bi] : 0;
+    // the exponents exact_fb left with record j (EXT): E_j, G_j
+    auto rec_exp = [&](int j) { return (const int32_t *)(a.x + xo[j] + 4ull * a.rec[roff[j]]); };
     // o(t): the side of state t of record j that carries the lower allele of locus k
     // (k < head_len: j is the head record; its hdr word carries locus 0 when head_len is 1)
     auto low_side = [&](const RecView &R, int k, int t) -> int {
@@ -1323,6 +1428,7 @@ __global__ __launch_bounds__(256) void exact_pair_posteriors(ExactArgs a, PairAr
         prev = cur;
         cur = x;
         const RecView R(a.rec + roff[j], false);
+        const int step = EXT ? rec_exp(j)[0] - rec_exp(j - 1)[0] : 0;
         for (int t = tid; t < R.F; t += NT) {
           const double tpv = R.tpv[t];
           double n0[NS], n1[NS];
@@ -1345,7 +1451,7 @@ __global__ __launch_bounds__(256) void exact_pair_posteriors(ExactArgs a, PairAr
           double2 *o = (double2 *)(cur + (size_t)t * 2 * NS);
 #pragma unroll
           for (int u = 0; u < NS; ++u)
-            if ((live >> u) & 1u) o[u] = make_double2(n0[u], n1[u]);
+            if ((live >> u) & 1u) o[u] = EXT ? make_double2(ldexp(n0[u], step), ldexp(n1[u], step)) : make_double2(n0[u], n1[u]);
         }
         __syncthreads();
         unread = false;
@@ -1355,6 +1461,11 @@ __global__ __launch_bounds__(256) void exact_pair_posteriors(ExactArgs a, PairAr
         if (!((live >> slot) & 1u) || ev.row < 0 || s0 + (unsigned long long)ev.row >= s1) continue;  // (none such)
         const unsigned long long row = s0 + (unsigned long long)ev.row;
         const double *bw = (const double *)(a.x + xo[j]) + R.F;
+        if constexpr (EXT) {
+          sc = EL - rec_exp(j)[0] - rec_exp(j)[1];
+          sa = sc / 2;
+          sb = sc - sa;
+        }
         for (int w = wave; w < 2; w += nw) {  // wave-uniform: 0 cis, 1 trans
           double part[1] = {0.0};
           for (int t = lane; t < R.F; t += WAVE)
@@ -1385,7 +1496,10 @@ __global__ __launch_bounds__(256) void exact_pair_posteriors(ExactArgs a, PairAr
 
 template <int NS>
 static hipError_t launch_pair(const ExactArgs &a, const PairArgs &s, int grid, hipStream_t st, int block) {
-  hipLaunchKernelGGL(exact_pair_posteriors<NS>, dim3(grid), dim3(block), (size_t)s.lds_states * 32 * NS, st, a, s);
+  if (a.extended)
+    hipLaunchKernelGGL((exact_pair_posteriors<NS, true>), dim3(grid), dim3(block), (size_t)s.lds_states * 32 * NS, st, a, s);
+  else
+    hipLaunchKernelGGL((exact_pair_posteriors<NS, false>), dim3(grid), dim3(block), (size_t)s.lds_states * 32 * NS, st, a, s);
   return hipGetLastError();
 }
 
@@ -1429,6 +1543,13 @@ hipError_t launch_exact_pair_posteriors(const ExactArgs &a, const PairArgs &s, i
 // the chosen contribution's rev flag after the state's two alleles are written.
 // prob = ((tpv of the states from record L down to the head, multiplied in
 // that order) x 2 if the two haplotypes differ) / P(genotype).
+// EXT (ExactArgs::extended): every choice compares running sums within one
+// record, all of whose values carry the same power of two, so the scaled
+// forward values give the same choices.  The running product of tpv is kept
+// as a mantissa in [0.5, 1) and a count of the powers of two taken out
+// (frexp: exact), the count cancels against the total's exponent E_L, and prob
+// is rounded by the division and, if subnormal, once more by the final ldexp.
+template <bool EXT>
 __global__ __launch_bounds__(DRAW_BLOCK) void exact_posterior_draws(ExactArgs a, DrawArgs s) {
   __shared__ double cs_lds[DRAW_LDS_CHUNKS];
   const int tid = threadIdx.x, lane = tid & (WAVE - 1), wave = tid / WAVE;
@@ -1441,9 +1562,9 @@ __global__ __launch_bounds__(DRAW_BLOCK) void exact_posterior_draws(ExactArgs a,
     const int d = dc * DRAW_BLOCK + tid;
     const int bi = a.order[q];
     const int st0 = a.status[bi];
-    const double pg = a.gprob[bi];
+    const double pg = EXT ? a.xtot[bi] : a.gprob[bi];
     const bool resolved = (st0 == EST_OK || st0 == EST_OK_PRUNED) && pg > 0.0 && !isinf(pg);
-    if (!resolved || pg < SITE_PG_MIN) {  // the host writes the input genotype: unresolved (1), P(genotype) subnormal (2)
+    if (!resolved || (!EXT && pg < SITE_PG_MIN)) {  // the host writes the input genotype: unresolved (1), P(genotype) subnormal (2)
       if (tid == 0 && dc == 0) s.status[q] = resolved ? 2 : 1;
       continue;
     }
@@ -1505,6 +1626,14 @@ __global__ __launch_bounds__(DRAW_BLOCK) void exact_posterior_draws(ExactArgs a,
     int par = 0;
     bool het = false, dead = false;
     double p = 1.0;
+    int pe = 0;  // EXT: the true product is p 2^pe
+    auto renorm = [&]() {
+      if constexpr (EXT) {
+        int e;
+        p = frexp(p, &e);
+        pe += e;
+      }
+    };
     for (int j = L; j > hl; --j) {
       const RecView R(a.rec + roff[j], false);
       const uint32_t hd = R.hdr[t], xa = hd & 0xFFu, xb = (hd >> 8) & 0xFFu;
@@ -1515,6 +1644,7 @@ __global__ __launch_bounds__(DRAW_BLOCK) void exact_posterior_draws(ExactArgs a,
       put(j - 1, par ^ 1, xb);
       het |= xa != xb;
       p = j == L ? tpv : p * tpv;
+      renorm();
       // the full sum: four contributions at a time, their words, then their
       // predecessors' forward values, then the terms in record order
       double tot = 0.0;
@@ -1562,6 +1692,7 @@ __global__ __launch_bounds__(DRAW_BLOCK) void exact_posterior_draws(ExactArgs a,
       const RecView H(a.rec + roff[hl], true);
       const double tpv = H.tpv[t];
       p = L == hl ? tpv : p * tpv;
+      renorm();
       if (hl == 1) {
         const uint32_t hd = H.hdr[t], xa = hd & 0xFFu, xb = (hd >> 8) & 0xFFu;
         put(0, par, xa);
@@ -1577,7 +1708,11 @@ __global__ __launch_bounds__(DRAW_BLOCK) void exact_posterior_draws(ExactArgs a,
         }
       }
     }
-    if (s.prob) s.prob[(size_t)q * D + d] = dead ? 0.0 : (het ? p * 2.0 : p) / pg;
+    if constexpr (EXT) {
+      if (s.prob) s.prob[(size_t)q * D + d] = dead ? 0.0 : ldexp((het ? p * 2.0 : p) / pg, pe + a.xtot_exp[bi]);
+    } else {
+      if (s.prob) s.prob[(size_t)q * D + d] = dead ? 0.0 : (het ? p * 2.0 : p) / pg;
+    }
   }
 }
 
@@ -1586,7 +1721,8 @@ hipError_t launch_exact_posterior_draws(const ExactArgs &a, const DrawArgs &s, i
   if (grid < 1 || s.draws < 1 || !s.status || s.lds_chunks < 0 ||
       s.lds_chunks > DRAW_LDS_CHUNKS || (s.csum && s.csum_stride < 1))
     return hipErrorInvalidValue;
-  hipLaunchKernelGGL(exact_posterior_draws, dim3(grid), dim3(DRAW_BLOCK), 0, st, a, s);
+  if (a.extended) hipLaunchKernelGGL(exact_posterior_draws<true>, dim3(grid), dim3(DRAW_BLOCK), 0, st, a, s);
+  else hipLaunchKernelGGL(exact_posterior_draws<false>, dim3(grid), dim3(DRAW_BLOCK), 0, st, a, s);
   return hipGetLastError();
 }
 

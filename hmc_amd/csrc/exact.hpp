@@ -37,6 +37,15 @@ struct ExactArgs {
   unsigned long long *acc_freq, *acc_prefix;  // [candidates] fixed point
   long long item0 = 0, item1 = -1;  // walk items [item0, item1) of n_order x L (individual-major); -1 = all
   bool forward_only = false;        // exact_fb leaves the backward values unwritten (the posterior draws never read them)
+  // Extended range (hmc_set_posterior_range, hmc_genotype_likelihoods; never the
+  // exact M-step): exact_fb keeps every record in range by exact powers of two.
+  // The x-store then holds fs_j[t] = fwd_j[t] 2^E_j and bs_j[t] = bwd_j[t] 2^G_j
+  // with every record's maximum in [0.5, 1), and the record's two spare words
+  // (after bwd[F]) hold E_j and G_j as int32.  Per individual, xtot = the sum of
+  // fs_L in state order from 0.0 and xtot_exp = E_L: P(genotype) = xtot 2^-E_L.
+  bool extended = false;
+  double *xtot = nullptr;           // [batch]
+  int32_t *xtot_exp = nullptr;      // [batch]
 };
 
 // Breadth-first trie walk (exact_walk_units): one lane per work unit — a trie

@@ -632,6 +632,38 @@ class HaploModel:
         self._check(lib().hmc_last_draw_stats(self._h, C.byref(s), C.byref(f), C.byref(k), C.byref(g), C.byref(p)))
         return dict(structure_ms=s.value, fb_ms=f.value, draw_ms=k.value, groups=g.value, n_pruned=p.value)
 
+    def set_posterior_range(self, extended: bool):
+        """Range of genotype_posteriors, switch_posteriors, pair_posteriors,
+        posterior_draws and their write_* forms (hmc_set_posterior_range).
+        False (default): raw doubles; individuals whose P(genotype) underflows
+        get status 1 or 2 and zeros.  True: the forward-backward pass rescales
+        every record by an exact power of two, so long panels get real rows:
+        no status 2, status 1 only for a lattice with no path."""
+        self._check(lib().hmc_set_posterior_range(self._h, 1 if extended else 0))
+
+    def genotype_likelihoods(self, indiv=None) -> dict:
+        """P(genotype) under the model of the last resolve_all as mantissa[n] x
+        2^exponent[n], mantissa in [0.5, 1), from the scaled forward pass
+        (hmc_genotype_likelihoods): the likelihood of individuals whose total
+        the E-step reports as 0 or subnormal.  indiv: panel indices (None =
+        this rank's whole shard).  status[n]: 0 ok; 1 no path, (0.0, 0)."""
+        if indiv is None:
+            qi, n = None, self.i1 - self.i0
+        else:
+            qi = np.ascontiguousarray(indiv, np.int32).reshape(-1)
+            n = len(qi)
+        out = dict(mantissa=np.zeros(n, np.float64), exponent=np.zeros(n, np.int32), status=np.zeros(n, np.int32))
+        self._check(lib().hmc_genotype_likelihoods(self._h, n, None if qi is None else _p(qi, C.c_int32),
+                                                   _p(out["mantissa"], C.c_double), _p(out["exponent"], C.c_int32),
+                                                   _p(out["status"], C.c_int32)))
+        return out
+
+    def likelihood_stats(self) -> dict:
+        """Device ms and groups of the last genotype_likelihoods (hmc_last_likelihood_stats)."""
+        s, f, g = C.c_double(), C.c_double(), C.c_int()
+        self._check(lib().hmc_last_likelihood_stats(self._h, C.byref(s), C.byref(f), C.byref(g)))
+        return dict(structure_ms=s.value, fb_ms=f.value, groups=g.value)
+
     def set_draw_tuning(self, lds_chunks: int = -1, forward_only: bool = True):
         """Test seam of posterior_draws (hmc_set_draw_tuning): the final
         record's prefix sums stay in LDS up to this many chunks of 64 states

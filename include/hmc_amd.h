@@ -431,6 +431,50 @@ int hmc_posterior_draws(hmc_ctx *ctx, int64_t n, const int32_t *indiv, int draws
  * kernel and of the draw kernel with its transposition; groups the individuals ran in;
  * individuals on pruned records.  Replaces no reference interface. */
 int hmc_last_draw_stats(const hmc_ctx *ctx, double *structure_ms, double *fb_ms, double *draw_ms, int *groups, int *n_pruned);
+/* Range of the posterior family (hmc_genotype_posteriors, hmc_switch_posteriors,
+ * hmc_pair_posteriors, hmc_posterior_draws and their hmc_write_* forms).
+ * extended = 0 (default): the forward-backward pass keeps raw doubles and
+ * divides by the last E-step's P(genotype); an individual whose P(genotype) is
+ * below DBL_MIN gets status 2, one whose forward likelihood underflowed to 0
+ * in the E-step status 1 — from about 1 200 loci on.
+ * extended = 1: the pass multiplies every record (the states after one locus)
+ * by the power of two that brings the record's largest value into [0.5, 1),
+ * forward and backward, and keeps the cumulative exponents; the divisor is
+ * the pass's own total, the final record's scaled forward values summed in
+ * state order, with its exponent, and the consumers cancel the exponents with
+ * ldexp.  Status 2 never occurs; status 1 only for a lattice with no path (the
+ * structure pass finds the individual unresolved, or the total is exactly 0);
+ * an individual the E-step gave up on for underflow gets status 0 and real
+ * rows, draws and prob (prob may be subnormal or 0 when the pair's posterior is
+ * that small); hmc_last_*_stats report n_pruned = 0.  The same HMC_EARG and
+ * HMC_EUNSUPPORTED conditions apply.
+ * Between the modes: scaling by powers of two is exact, so an extended result
+ * depends on the real-valued posterior and the summation order alone, not on
+ * where the rescalings fall; multiplying every freq and tp of the table by one
+ * power of two changes no bit of any extended result.  Where the regular mode
+ * gives status 0 and none of its intermediates is subnormal, the two modes
+ * differ only through the divisor — the E-step's P(genotype) against the sum
+ * of this pass's own final forward values — and agree within the sum of their
+ * rounding bounds; they are byte-identical exactly where those two totals are.
+ * The setting changes no E-step, M-step or later result.  HMC_EARG for any
+ * other value.  Replaces no reference interface. */
+int hmc_set_posterior_range(hmc_ctx *ctx, int extended);
+/* P(genotype) of individuals under the model of the last E-step in extended
+ * range: mantissa[q] x 2^exponent[q] with mantissa in [0.5, 1) — the
+ * likelihood the E-step reports as 0 or subnormal on long panels.  Always the
+ * scaled forward pass, whatever hmc_set_posterior_range says; forward only, as
+ * the draws.  indiv[n] are panel indices inside this rank's shard, any order,
+ * repeats allowed; indiv = NULL means the whole shard (n is ignored).  Any
+ * output may be NULL.  status 0 ok; 1 the lattice has no path: (0.0, 0).  The
+ * value is the sum of the final record's forward values in state order (each
+ * the ordered sum exact_fb computes), which need not be the E-step's total to
+ * the last bit.  n = 0 is HMC_OK with no device work.  HMC_EARG and
+ * HMC_EUNSUPPORTED as for hmc_posterior_draws.  Replaces no reference interface. */
+int hmc_genotype_likelihoods(hmc_ctx *ctx, int64_t n, const int32_t *indiv, double *mantissa, int32_t *exponent,
+                             int32_t *status);
+/* Last hmc_genotype_likelihoods: device ms of its structure passes and of the
+ * forward kernel; groups.  Replaces no reference interface. */
+int hmc_last_likelihood_stats(const hmc_ctx *ctx, double *structure_ms, double *fb_ms, int *groups);
 /* ---- whole EM: HaploModel::run (HaploModel.cpp:117-155) ------------------ */
 typedef struct hmc_iter_log {
   double log_likelihood;

@@ -22,6 +22,7 @@ struct Options {
   int draws = 100;                     // --draws D (>= 1)
   unsigned long long seed = 0;         // --seed S
   bool have_draws = false, have_seed = false;
+  bool extended_range = false;         // --extended-range (needs one of the --output-*posteriors / --output-draws options)
 };
 
 // --output-posteriors (no reference counterpart): <first file>.posteriors, the
@@ -52,7 +53,9 @@ constexpr const char *USAGE =
     "                        individual's heterozygous loci at most K heterozygous loci apart (K >= 1)\n"
     "  --output-draws FILE [--draws D] [--seed S]  write FILE: D haplotype pairs per individual drawn\n"
     "                        from the exact posterior under the final model, each with its posterior\n"
-    "                        (default D = 100, S = 0; a draw depends on S, the individual and its index)";
+    "                        (default D = 100, S = 0; a draw depends on S, the individual and its index)\n"
+    "  --extended-range      the four options above in extended range: individuals whose likelihood\n"
+    "                        underflows a double (panels of more than about 1 200 loci) get lines too";
 
 // 0 on success; otherwise `err` says what is wrong (a missing value, an
 // unknown option, no data file).
@@ -85,6 +88,7 @@ inline int parse_options(int argc, const char *const *argv, Options &o, std::str
     else if (a == "--pair-span") { if (!next()) return 1; o.pair_span = atoi(v); o.have_pair_span = true; }
     else if (a == "--output-draws") { if (!next()) return 1; o.output_draws = v; }
     else if (a == "--draws") { if (!next()) return 1; o.draws = atoi(v); o.have_draws = true; }
+    else if (a == "--extended-range") o.extended_range = true;
     else if (a == "--seed") { if (!next()) return 1; o.seed = strtoull(v, nullptr, 10); o.have_seed = true; }
     else if (a == "-m" || a == "--model") { if (!next()) return 1; o.model = v; }          // HMC.cpp:35
     else if (a == "-o" || a == "--mc-order") { if (!next()) return 1; o.mc_order = atoi(v); }      // HMC.cpp:41
@@ -110,6 +114,12 @@ inline int parse_options(int argc, const char *const *argv, Options &o, std::str
   }
   if ((o.have_draws || o.have_seed) && o.output_draws.empty()) {
     err = "--draws and --seed need --output-draws FILE\n" + std::string(USAGE);
+    return 1;
+  }
+  if (o.extended_range && !o.output_posteriors && !o.output_switch_posteriors && o.output_pair_posteriors.empty() &&
+      o.output_draws.empty()) {
+    err = "--extended-range needs --output-posteriors, --output-switch-posteriors, --output-pair-posteriors or --output-draws\n" +
+          std::string(USAGE);
     return 1;
   }
   return 0;

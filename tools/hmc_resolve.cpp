@@ -12,7 +12,7 @@
 //               [--sample-size 10] [--min-pattern-len 1] [--max-pattern-len 30]
 //               [--output-patterns x] [--output-posteriors] [--output-switch-posteriors]
 //               [--output-pair-posteriors FILE --pair-span K]
-//               [--output-draws FILE [--draws 100] [--seed 0]] [--device 0] datafile ...
+//               [--output-draws FILE [--draws 100] [--seed 0]] [--extended-range] [--device 0] datafile ...
 // --output-posteriors (no reference counterpart) writes <first file>.posteriors:
 // genotype posteriors at the loci with a missing input allele, under the final
 // model (hmc_write_posteriors).  --output-switch-posteriors (none either)
@@ -24,6 +24,9 @@
 // --output-draws FILE [--draws D] [--seed S] (none either) writes FILE: D
 // haplotype pairs per individual drawn from the exact posterior under the
 // final model, each with its posterior (hmc_write_posterior_draws).
+// --extended-range (none either) runs those four in extended range
+// (hmc_set_posterior_range): individuals whose likelihood underflows a double
+// get lines too.
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -90,6 +93,7 @@ int main(int argc, char **argv) {
     const std::string pf = files[0] + ".patterns";
     if ((rc = hmc_write_patterns(ctx, pf.c_str()))) die("hmc_write_patterns");
   }
+  if ((rc = hmc_set_posterior_range(ctx, o.extended_range ? 1 : 0))) die("hmc_set_posterior_range");
   if (o.output_posteriors) {  // of the run's last E-step: hmc_run ends on an E-step of the final model
     const std::string qf = files[0] + ".posteriors";
     if ((rc = hmc_write_posteriors(ctx, qf.c_str()))) die("hmc_write_posteriors");
