@@ -39,6 +39,7 @@ namespace {
 
 constexpr unsigned long long REC_CHUNK = 1ull << 16;  // record words per bump allocation
 constexpr int NBUCKET = 32;                           // chain-length buckets (longest first)
+constexpr uint32_t NS_CHAIN = 1u << 31;               // F_NS of a chain state after the sweep: flag | contributions
 
 // An array whose entries [0, fc) live in LDS and [fc, ..) in HBM scratch.
 template <class T>
@@ -336,6 +337,25 @@ size_t estep_s1_lds_bytes(int fc, int hc, int cc, int amax, int nw) {
 // NW wavefronts per individual: one wave (many individuals per CU) or four
 // (the first E-step's large frontiers: 4x the LDS tier and 4x the
 // contributions per step of the extendAll scan).
+//
+// Per locus:
+//   pairs   the allele pairs in extendAll call order.  Without a missing
+//           allele (block-uniform) the one pair stays in registers; else
+//           thread 0 lists them in LDS and a barrier hands them over.
+//   chunks  NT contributions at a time: successor gathers, key insert, rank
+//           among the chunk's equal keys, new states in creation order.  The
+//           block scan that numbers the new states also counts the chunk's
+//           valid contributions, so Cv (the record's contribution words) is
+//           known when the loop ends and the record is allocated there.
+//   sweep   one pass over the new states, NT per round: slot count and
+//           pattern-table fields read together, the counts scanned over the
+//           block while the gathers are in flight, then first-contribution
+//           position, list length, record fields, chain bucket, and the
+//           slot's key / count / tag cleared for the next locus.  A chain
+//           state keeps its count in its F_NS word (NS_CHAIN) for the chain list.
+//   chains  bucket offsets (longest first), chain list, contributions in add
+//           order; prune mode then sums the new states' forward likelihoods.
+//   The locus ends in its one barrier between the clears and the next insert.
 template <int NW>
 __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(3))) void estep_structure(StructArgs a) {
   extern __shared__ __align__(16) unsigned char smem[];
@@ -542,7 +562,13 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(3))) vo
     for (int i = from_ck ? wlo - 1 : hl; i < whi - 1 && status == EST_OK; ++i) {
       if (Fp == 0) { status = EST_UNRESOLVED; break; }
       const uchar2 gg = g[i];
-      if (tid == 0) {  // allele-pair list in extendAll call order
+      // no missing allele (block-uniform): the one pair (x, y) and its
+      // orientation count stay in registers, no list and no hand-off
+      const bool one_pair = gg.x != MISSING && gg.y != MISSING;
+      const uint32_t px = gg.x, py = gg.y;
+      const int po = gg.x == gg.y ? 1 : 2;
+      if (tid < NBUCKET) bucket[tid] = 0;  // chain buckets of this locus (first read after the chunk loop)
+      if (!one_pair && tid == 0) {  // allele-pair list in extendAll call order
         const double *af = a.pan.afreq + (size_t)i * amax;
         const int an = a.pan.anum[i];
         int np = 0;
@@ -555,20 +581,18 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(3))) vo
         } else if (gg.x == MISSING) {
           for (int j = 0; j < an; ++j)
             if (af[j] > 0) push(j, gg.y);
-        } else if (gg.y == MISSING) {
+        } else {
           for (int j = 0; j < an; ++j)
             if (af[j] > 0) push(j, gg.x);
-        } else {
-          push(gg.x, gg.y);
         }
         int off = 0;
         for (int p = 0; p < np; ++p) { pr_off[p] = off; off += Fp * pr_o[p]; }
         pr_off[np] = off;
         pr_off[npm + 1] = np;
       }
-      B.sync();
-      const int npairs = pr_off[npm + 1];
-      const int C = pr_off[npairs];
+      if (!one_pair) B.sync();
+      const int npairs = one_pair ? 1 : pr_off[npm + 1];
+      const int C = one_pair ? Fp * po : pr_off[npairs];
       if (C > a.ccap) { status = EST_OVERFLOW_CONTRIB; break; }
       // (LID: chunk tags must stay below 2^(32 - LID_BITS); the host then fails loudly)
       if (NW <= 4 && (long long)C >= ((1ll << (32 - LID_BITS)) - 1) * NT) { status = EST_OVERFLOW_CONTRIB; break; }
@@ -577,6 +601,7 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(3))) vo
       S1_CNT(9, Fp);
       S1_CNT(13, 1);
       int Fn = 0;
+      int Cv = 0;  // valid contributions = the sum of the slot counts = the record's contribution words
       // successor gathers of up to GB chunks issued together (one exposed
       // latency per GB*NT contributions), then the chunks' keys in order
       constexpr int GB = 4;
@@ -591,13 +616,20 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(3))) vo
             g_sa[q] = g_sb[q] = NONE;
             g_s[q] = 0;
             if (cq < C) {
-              int p = 0;
-              while (p + 1 < npairs && cq >= pr_off[p + 1]) ++p;
-              const int local = cq - pr_off[p];
-              const int o = pr_o[p] == 2 ? (local & 1) : 0;
-              g_s[q] = pr_o[p] == 2 ? (uint32_t)(local >> 1) : (uint32_t)local;
-              const uint32_t x = o ? pr_y[p] : pr_x[p];
-              const uint32_t y = o ? pr_x[p] : pr_y[p];
+              int local = cq, po_p = po;
+              uint32_t x_p = px, y_p = py;
+              if (!one_pair) {
+                int p = 0;
+                while (p + 1 < npairs && cq >= pr_off[p + 1]) ++p;
+                local = cq - pr_off[p];
+                po_p = pr_o[p];
+                x_p = pr_x[p];
+                y_p = pr_y[p];
+              }
+              const int o = po_p == 2 ? (local & 1) : 0;
+              g_s[q] = po_p == 2 ? (uint32_t)(local >> 1) : (uint32_t)local;
+              const uint32_t x = o ? y_p : x_p;
+              const uint32_t y = o ? x_p : y_p;
               g_sa[q] = SUCC[(size_t)*X.at(F_LO, (int)g_s[q]) * amax + x];
               g_sb[q] = SUCC[(size_t)*X.at(F_HI, (int)g_s[q]) * amax + y];
             }
@@ -670,8 +702,12 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(3))) vo
           for (int w = 0; w < NW; ++w) lw[w] = 0ull;
         }
         const bool is_new = valid && cnt0 == 0 && li == 0;
-        int nnew = 0;
-        const int rk_new = B.scan(is_new ? 1 : 0, &nnew);
+        // one scan carries both counts of the chunk (NT <= 1024: 16 bits each):
+        // its new states, and its valid contributions for Cv
+        int tot2 = 0;
+        const int rk_new = B.scan((is_new ? 1 : 0) | (valid ? 1 << 16 : 0), &tot2) & 0xFFFF;
+        const int nnew = tot2 & 0xFFFF;
+        Cv += tot2 >> 16;
         S1_ST(17);
         if (Fn + nnew > a.fcap) { status = EST_OVERFLOW_FRONTIER; break; }
         uint32_t st = 0;
@@ -701,17 +737,8 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(3))) vo
       S1_ST(1);
       S1_CNT(12, Fn > X.fc ? Fn - X.fc : 0);
 
-      // contributions per state -> first position (exclusive scan, creation order)
-      int Cv = 0;
-      for (int t0 = 0; t0 < Fn; t0 += NT) {
-        const int t = t0 + tid;
-        const int m = t < Fn ? (int)kcnt(*Y.at(F_SLOT, t)) : 0;
-        int tot = 0;
-        const int ex = B.scan(m, &tot);
-        if (t < Fn) *Y.at(F_CB, t) = (uint32_t)(Cv + ex);
-        Cv += tot;
-      }
-      S1_ST(18);
+      // Cv is known from the chunk loop, so the record is allocated before
+      // the sweep over the new states
       const unsigned long long words =
           4 + 4ull * Fn + 1 + (unsigned long long)Cv + Fn + (a.exact ? (unsigned long long)C + npairs : 0ull);
       rneed += (words + 1) & ~1ull;
@@ -721,32 +748,61 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(3))) vo
       uint32_t *R = a.rec + (counting ? 0 : o);  // not dereferenced while counting
       double *Rtp = (double *)(R + 4);
       uint32_t *Rhd = R + 4 + 2 * Fn, *Rcb = Rhd + Fn, *Rct = Rcb + Fn + 1, *Rch = Rct + Cv;
-      if (tid < NBUCKET) bucket[tid] = 0;
-      B.sync();
       S1_ST(19);
-      // per state: k-best list length min(S, sum of predecessor lengths) (the
-      // adds keep S once they overflow, HaploPair.cpp:85-88), tp product, last
-      // alleles; states whose lists overflow get a chain entry
+      // One sweep over the new states, NT per round.  A round issues its reads
+      // together — the state's ids, slot and predecessor-length sum, the slot's
+      // count, and the pattern table's tp / last allele of both ids — and scans
+      // the counts over the block (first contribution's position, creation
+      // order) while the table gathers are in flight.  Then per state: k-best
+      // list length min(S, sum of predecessor lengths) (the adds keep S once
+      // they overflow, HaploPair.cpp:85-88), tp product, last alleles; a state
+      // whose list overflows is counted in its chain bucket and keeps its count
+      // in the NS word for the chain list; the slot is cleared for the next
+      // locus (m_best_pair.clear()) as soon as its count is in the register.
+      int cb0 = 0;
       for (int t0 = 0; t0 < Fn; t0 += NT) {
         const int t = t0 + tid;
-        if (t < Fn) {
-          const uint32_t lo = *Y.at(F_LO, t), hi = *Y.at(F_HI, t);
-          const uint32_t nsum = t < Y.fc ? *Y.at(F_NS, t) : ld_acq(Y.at(F_NS, t));
+        const bool act = t < Fn;
+        uint32_t sl = 0, lo = 0, hi = 0, nsum = 0, al = 0, ah = 0;
+        int m = 0;
+        double tpl = 0.0, tph = 0.0;
+        if (act) {
+          sl = *Y.at(F_SLOT, t);
+          lo = *Y.at(F_LO, t);
+          hi = *Y.at(F_HI, t);
+          nsum = t < Y.fc ? *Y.at(F_NS, t) : ld_acq(Y.at(F_NS, t));
+          m = (int)kcnt(sl);
+          if (!counting) {
+            tpl = TP[lo];
+            tph = TP[hi];
+            al = LAST[lo];
+            ah = LAST[hi];
+          }
+        }
+        int tot = 0;
+        const int ex = B.scan(m, &tot);
+        if (act) {
+          const uint32_t cb = (uint32_t)(cb0 + ex);
           const uint32_t nl = nsum < (uint32_t)S ? nsum : (uint32_t)S;
+          *Y.at(F_CB, t) = cb;
           *Y.at(F_NL, t) = nl;
           re += nl;
           if (!counting) {
-            Rtp[t] = TP[lo] * TP[hi];  // m_transition_prob, HaploPair.cpp:42
+            Rtp[t] = tpl * tph;  // m_transition_prob, HaploPair.cpp:42
             // bit 27: the state's adds overflow S (a chain; the dataflow value pass
             // takes the chains first, estep_df.hip)
-            Rhd[t] = (uint32_t)LAST[lo] | (uint32_t)LAST[hi] << 8 | nl << 16 | (nsum > (uint32_t)S ? HDR_CHAIN : 0u);
-            Rcb[t] = *Y.at(F_CB, t);
+            Rhd[t] = al | ah << 8 | nl << 16 | (nsum > (uint32_t)S ? HDR_CHAIN : 0u);
+            Rcb[t] = cb;
+            if (nsum > (uint32_t)S) {  // bucket 0 = most contributions
+              atomicAdd(&bucket[NBUCKET - 1 - (m - 1 < NBUCKET - 1 ? m - 1 : NBUCKET - 1)], 1);
+              *Y.at(F_NS, t) = NS_CHAIN | (uint32_t)m;  // the sum is consumed: the count, for the chain list
+            }
           }
-          if (!counting && nsum > (uint32_t)S) {  // bucket 0 = most contributions
-            const int m = (int)kcnt(*Y.at(F_SLOT, t));
-            atomicAdd(&bucket[NBUCKET - 1 - (m - 1 < NBUCKET - 1 ? m - 1 : NBUCKET - 1)], 1);
-          }
+          *K.key(sl) = KEY_EMPTY;
+          *K.cnt(sl) = 0;
+          if constexpr (LID) *K.tag(sl) = 0u;
         }
+        cb0 += tot;
       }
       B.sync();
       S1_ST(2);
@@ -759,12 +815,13 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(3))) vo
         if (wv == 0 && lane < NBUCKET) bucket[lane] = incl - b;
       }
       B.sync();
+      S1_ST(18);
       for (int t0 = 0; t0 < Fn && !counting; t0 += NT) {
         const int t = t0 + tid;
         if (t < Fn) {
-          const uint32_t nsum = t < Y.fc ? *Y.at(F_NS, t) : ld_acq(Y.at(F_NS, t));
-          if (nsum > (uint32_t)S) {
-            const int m = (int)kcnt(*Y.at(F_SLOT, t));
+          const uint32_t w = t < Y.fc ? *Y.at(F_NS, t) : ld_acq(Y.at(F_NS, t));
+          if (w & NS_CHAIN) {  // left by the sweep: the state's contributions
+            const int m = (int)(w & ~NS_CHAIN);
             const int pos = atomicAdd(&bucket[NBUCKET - 1 - (m - 1 < NBUCKET - 1 ? m - 1 : NBUCKET - 1)], 1);
             Rch[pos] = (uint32_t)t;
           }
@@ -788,7 +845,7 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(3))) vo
         }
       }
       if (a.exact && !counting)
-        for (int p = tid; p < npairs; p += NT) Rout[C + p] = pr_o[p];
+        for (int p = tid; p < npairs; p += NT) Rout[C + p] = one_pair ? (uint32_t)po : (uint32_t)pr_o[p];
       if (tid == 0 && !counting) {
         Rcb[Fn] = (uint32_t)Cv;
         R[0] = (uint32_t)Fn;
@@ -813,16 +870,8 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(3))) vo
           fwy[t] = f;
         }
       }
-      // m_best_pair.clear() for the next locus
-      for (int t0 = 0; t0 < Fn; t0 += NT) {
-        const int t = t0 + tid;
-        if (t < Fn) {
-          const uint32_t sl = *Y.at(F_SLOT, t);
-          *K.key(sl) = KEY_EMPTY;
-          *K.cnt(sl) = 0;
-          if constexpr (LID) *K.tag(sl) = 0u;
-        }
-      }
+      // the locus's last barrier: the sweep's slot clears, the bucket and pair
+      // words and this frontier's reads, before the next locus's first insert
       B.sync();
       const IdFront1 T = X;
       X = Y;
@@ -885,7 +934,7 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(3))) vo
 // ======================================================= pass 1, v2 ======
 //
 // The same structure records with fewer block-wide hand-offs per locus
-// (estep_structure: ~26 barriers per locus, five per chunk of NT
+// (estep_structure: ~25 barriers per locus, five per chunk of NT
 // contributions, which the cfg 3 E1 stamps show as the pass's cost).  Each
 // thread owns a contiguous run of the locus's contributions in extendAll
 // order and a contiguous run of the new states, so creation order and each

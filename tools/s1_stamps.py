@@ -20,8 +20,9 @@ m = hmc_amd.HaploModel()
 m.load(hmc_amd.GenoData.from_panel(p))
 m.find_patterns()
 names = {0: "pairs", 14: "chunk: gathers", 15: "chunk: keys+lanes", 16: "chunk: rank sync",
-         17: "chunk: new-state scan", 7: "chunk: states+records", 1: "after the chunks", 18: "counts scan",
-         19: "record alloc", 2: "per-state loop", 3: "chains/order", 4: "clear", 5: "head", 6: "epilogue"}
+         17: "chunk: new-state scan", 7: "chunk: states+records", 1: "after the chunks", 19: "record alloc",
+         2: "state sweep (+clear)", 18: "bucket scan", 3: "chain list/order", 4: "prune, end barrier", 5: "head",
+         6: "epilogue"}
 for it in range(iters):
     m.resolve_all()
     st = (C.c_uint64 * 40)()
