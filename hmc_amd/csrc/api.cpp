@@ -988,6 +988,40 @@ int hmc_set_pair_tuning(hmc_ctx *h, int slots, int tier_states) {
   return HMC_OK;
 }
 
+int hmc_haplotype_dosages(hmc_ctx *h, int64_t n, const int32_t *indiv, int n_patterns, const int32_t *start, const int32_t *len,
+                          int maxlen, const int32_t *alleles_a, const int32_t *alleles_b, double *dosage, int32_t *status) {
+  if (!h) return HMC_EARG;
+  Ctx &c = h->c;
+  if (!c.have_panel) return c.fail(HMC_EARG, "no panel loaded");
+  return c.haplotype_dosages(n, indiv, n_patterns, start, len, maxlen, alleles_a, alleles_b, dosage, status);
+}
+
+int hmc_last_dosage_stats(const hmc_ctx *h, double *structure_ms, double *fb_ms, double *sweep_ms, int *groups, int *n_pruned,
+                          int *n_spilled, int *slots, int *rounds) {
+  if (!h) return HMC_EARG;
+  if (structure_ms) *structure_ms = h->c.ds_ms_struct;
+  if (fb_ms) *fb_ms = h->c.ds_ms_fb;
+  if (sweep_ms) *sweep_ms = h->c.ds_ms_sweep;
+  if (groups) *groups = h->c.ds_groups;
+  if (n_pruned) *n_pruned = h->c.ds_pruned;
+  if (n_spilled) *n_spilled = h->c.ds_spilled;
+  if (slots) *slots = h->c.ds_ns;
+  if (rounds) *rounds = h->c.ds_rounds;
+  return HMC_OK;
+}
+
+int hmc_set_dosage_tuning(hmc_ctx *h, int slots, int tier_states) {
+  if (!h) return HMC_EARG;
+  if (slots != 0 && !hmc::pair_slots_ok(slots))
+    return h->c.fail(HMC_EARG, "dosage tuning: %d slots are not instantiated (1, 2, 4 or 8; 0 = automatic)", slots);
+  if (tier_states < 0 || tier_states > hmc::pair_tier_max(hmc::PAIR_SLOTS_MAX))
+    return h->c.fail(HMC_EARG, "dosage tuning: a tier of %d states is outside [0, %d]", tier_states,
+                     hmc::pair_tier_max(hmc::PAIR_SLOTS_MAX));
+  h->c.ds_slots = slots;
+  h->c.ds_tier = tier_states;
+  return HMC_OK;
+}
+
 int hmc_posterior_draws(hmc_ctx *h, int64_t n, const int32_t *indiv, int draws, uint64_t seed, int32_t *hap, double *prob,
                         int32_t *status) {
   if (!h) return HMC_EARG;
@@ -1215,6 +1249,43 @@ int hmc_write_pair_posteriors(hmc_ctx *h, const char *path, int span) {
     put_lower(indiv[q], la[q]);
     put_lower(indiv[q], lb[q]);
     fprintf(fp, "\t%.17g\t%.17g\n", post[2 * q], post[2 * q + 1]);
+  }
+  const bool bad = ferror(fp) != 0;
+  if (fclose(fp) != 0 || bad) return c.fail(HMC_EIO, "Can not write file %s!", path);
+  return HMC_OK;
+}
+
+int hmc_write_haplotype_dosages(hmc_ctx *h, const char *path, int n_patterns, const char *const *names, const int32_t *start,
+                                const int32_t *len, int maxlen, const int32_t *alleles_a, const int32_t *alleles_b) {
+  if (!h || !path || !h->c.have_panel) return HMC_EARG;
+  Ctx &c = h->c;
+  if (n_patterns < 0 || (n_patterns > 0 && !names)) return c.fail(HMC_EARG, "haplotype dosages: no pattern names given");
+  const int n = c.nloc(), P = n_patterns;
+  // individuals in batches whose rows take at most 64 MiB of host memory; a row does not depend on the
+  // other individuals of its call, so the lines are those of one call for the shard
+  const int nb = (int)std::max<size_t>(1, std::min<size_t>((size_t)std::max(n, 1), ((size_t)8 << 20) / (size_t)std::max(P, 1)));
+  std::vector<int32_t> status(nb), indiv(nb);
+  std::vector<double> dose((size_t)nb * P);
+  FILE *fp = nullptr;
+  hmc::FileData d;
+  for (int b0 = 0; b0 < n || !fp; b0 += nb) {
+    const int k = std::max(0, std::min(nb, n - b0));
+    for (int i = 0; i < k; ++i) indiv[i] = c.i0 + b0 + i;
+    int rc;
+    // (the first batch before the file is opened: a call that fails leaves no file behind)
+    if ((rc = c.haplotype_dosages(k, indiv.data(), P, start, len, maxlen, alleles_a, alleles_b, dose.data(), status.data()))) {
+      if (fp) fclose(fp);
+      return rc;
+    }
+    if (!fp) {
+      if (!(fp = fopen(path, "w"))) return c.fail(HMC_EIO, "Can not open file %s!", path);
+      d = writer_meta(c);
+      fprintf(fp, "Id\tHaplotype\tDosage\n");
+    }
+    for (int i = 0; i < k; ++i) {
+      if (status[i] != 0 || P == 0) continue;
+      for (int p = 0; p < P; ++p) fprintf(fp, "%s\t%s\t%.17g\n", d.ids[indiv[i]].c_str(), names[p], dose[(size_t)i * P + p]);
+    }
   }
   const bool bad = ferror(fp) != 0;
   if (fclose(fp) != 0 || bad) return c.fail(HMC_EIO, "Can not write file %s!", path);

@@ -809,7 +809,7 @@ struct Ctx {
   void site_list(SiteList &sl) const;
   int site_group(const ExactArgs &x, int k, int dev_cu);
   // what the exact group runs after exact_fb in place of the trie walk
-  enum XpMode { XP_OFF = 0, XP_GENOTYPE = 1, XP_SWITCH = 2, XP_PAIR = 3, XP_DRAW = 4, XP_LIK = 5 };
+  enum XpMode { XP_OFF = 0, XP_GENOTYPE = 1, XP_SWITCH = 2, XP_PAIR = 3, XP_DRAW = 4, XP_LIK = 5, XP_DOSE = 6 };
   XpMode xp_mode = XP_OFF;
   // Extended range (hmc_set_posterior_range): the four posterior calls run
   // exact_fb's scaled pass (ExactArgs::extended) and divide by its own total,
@@ -879,6 +879,31 @@ struct Ctx {
   // of the last call, as sw_* above; pr_ns: the NS used, pr_rounds: most rounds of any individual
   double pr_ms_struct = 0, pr_ms_fb = 0, pr_ms_sweep = 0;
   int pr_groups = 0, pr_pruned = 0, pr_spilled = 0, pr_ns = 0, pr_rounds = 0;
+  // Haplotype dosages (hmc_haplotype_dosages): expected copies of caller-given
+  // patterns (window, allele rows A and B) per asked individual;
+  // exact_haplotype_dosages per group (XP_DOSE), in batches whose device
+  // output stays within DOSE_OUT_BYTES.  The pattern set is the same for every
+  // individual, so one plan (dosage_plan.hpp) serves the call.  Rows are the
+  // caller's: an individual asked for twice is swept once and copied.
+  int haplotype_dosages(int64_t n, const int32_t *indiv, int n_patterns, const int32_t *start, const int32_t *len, int maxlen,
+                        const int32_t *alleles_a, const int32_t *alleles_b, double *dosage, int32_t *status);
+  int dosage_group(const ExactArgs &x, const int32_t *ids, const std::vector<int32_t> &fm, int k, int dev_cu);
+  static constexpr size_t DOSE_OUT_BYTES = (size_t)512 << 20;
+  struct DoseCall {  // the running call
+    int P = 0, maxlen = 0, n_events = 0;
+    double *dosage = nullptr;
+    std::vector<int64_t> row_off, rows;  // CSR over the shard's individuals: the caller's rows that ask for each
+    std::vector<int32_t> status;         // [shard] 1 until the individual's group has run
+  } ds;
+  DevBuf<DoseEvent> d_ds_ev;
+  DevBuf<uint8_t> d_ds_codes;
+  DevBuf<double> d_ds_out, d_ds_scratch;
+  DevBuf<int32_t> d_ds_order, d_ds_status;
+  int ds_slots = 0, ds_tier = 0;  // hmc_set_dosage_tuning (0: automatic)
+  int ds_ns_run = 0;              // NS of the running call
+  // of the last call, as pr_* above; ds_rounds: sweeps over the records the plan takes
+  double ds_ms_struct = 0, ds_ms_fb = 0, ds_ms_sweep = 0;
+  int ds_groups = 0, ds_pruned = 0, ds_spilled = 0, ds_ns = 0, ds_rounds = 0;
   // Posterior draws (hmc_posterior_draws): `draws` haplotype pairs per asked
   // individual, sampled backwards through exact_fb's forward values;
   // exact_posterior_draws per group (XP_DRAW), in batches whose device output

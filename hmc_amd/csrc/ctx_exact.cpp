@@ -261,6 +261,7 @@ int Ctx::exact_group(const int32_t *ids, int k, const std::function<int(std::vec
   if (xp_mode == XP_SWITCH) return switch_group(x, ids, fm, k, dev_cu);
   if (xp_mode == XP_PAIR) return pair_group(x, ids, fm, k, dev_cu);
   if (xp_mode == XP_DRAW) return draw_group(x, ids, k, dev_cu);
+  if (xp_mode == XP_DOSE) return dosage_group(x, ids, fm, k, dev_cu);
   if (xp_mode == XP_LIK) {  // the scaled totals of the group's individuals: nothing runs after exact_fb
     std::vector<double> tot(n);
     std::vector<int32_t> ex(n);
@@ -689,6 +690,165 @@ int Ctx::draw_group(const ExactArgs &x, const int32_t *ids, int k, int dev_cu) {
   return HMC_OK;
 }
 
+int Ctx::dosage_group(const ExactArgs &x, const int32_t *ids, const std::vector<int32_t> &fm, int k, int dev_cu) {
+  const int NS = ds_ns_run, P = ds.P;
+  std::vector<int32_t> sel;  // the group's individuals that the caller asked for
+  for (int q = 0; q < k; ++q)
+    if (ds.row_off[ids[q] + 1] > ds.row_off[ids[q]]) sel.push_back(ids[q]);
+  if (sel.empty()) return HMC_OK;
+  const size_t cap = std::max<size_t>(1, DOSE_OUT_BYTES / ((size_t)P * 8));  // individuals per batch of output rows
+  DoseArgs s;
+  s.ev = d_ds_ev.p;
+  s.n_events = ds.n_events;
+  s.codes = d_ds_codes.p;
+  s.n_patterns = P;
+  s.maxlen = ds.maxlen;
+  s.tier = ds_tier > 0 ? ds_tier : PAIR_TIER_DEFAULT;
+  s.lds_states = std::max(1, std::min(s.tier, x.fmax));  // no more LDS than the group's largest record asks for
+  hipError_t e;
+  int spilled = 0;
+  for (int bi : sel) spilled += fm[bi] > s.tier;
+  ds_spilled += spilled;
+  std::vector<int32_t> h_st;
+  std::vector<double> h_out;
+  for (size_t pos = 0; pos < sel.size(); pos += cap) {
+    const int nb = (int)std::min(cap, sel.size() - pos);
+    int grid = std::max(1, std::min(nb, dev_cu * 8));
+    if (spilled) {  // frontiers past the tier: 32 NS B per state and block in HBM, at most 1 GiB (the grid does not change the bits)
+      grid = (int)std::max<size_t>(1, std::min<size_t>((size_t)grid, ((size_t)1 << 30) / ((size_t)32 * NS * x.fmax)));
+      if ((e = d_ds_scratch.ensure((size_t)grid * 4 * NS * x.fmax))) return hipfail(e, "exact_haplotype_dosages");
+      s.scratch = d_ds_scratch.p;
+      s.scratch_states = x.fmax;
+    }
+    if ((e = d_ds_order.ensure(nb)) || (e = d_ds_status.ensure(nb)) || (e = d_ds_out.ensure((size_t)nb * P)) ||
+        (e = hipMemsetAsync(d_ds_status.p, 0, (size_t)nb * 4, st)) || (e = hipMemsetAsync(d_ds_out.p, 0, (size_t)nb * P * 8, st)))
+      return hipfail(e, "exact_haplotype_dosages");
+    int rc;
+    if ((rc = upload_order(d_ds_order, sel.data() + pos, nb))) return rc;
+    ExactArgs xb = x;
+    xb.order = d_ds_order.p;
+    xb.n_order = nb;
+    s.dosage = d_ds_out.p;
+    s.status = d_ds_status.p;
+    hipEventRecord(ev[0], st);
+    if ((e = launch_exact_haplotype_dosages(xb, s, NS, grid, st))) return hipfail(e, "exact_haplotype_dosages");
+    hipEventRecord(ev[1], st);
+    h_st.resize(nb);
+    h_out.resize((size_t)nb * P);
+    if ((e = hipMemcpyAsync(h_st.data(), d_ds_status.p, (size_t)nb * 4, hipMemcpyDeviceToHost, st)) ||
+        (e = hipMemcpyAsync(h_out.data(), d_ds_out.p, (size_t)nb * P * 8, hipMemcpyDeviceToHost, st)) || (e = sync_st()))
+      return hipfail(e, "exact_haplotype_dosages");
+    float ms = 0;
+    hipEventElapsedTime(&ms, ev[0], ev[1]);
+    xp_ms_sites += ms;
+    for (int u = 0; u < nb; ++u) {
+      const int bi = sel[pos + u];
+      ds.status[bi] = h_st[u];
+      if (h_st[u] != 0 || !ds.dosage) continue;  // (the caller's rows get zeros)
+      for (int64_t w = ds.row_off[bi]; w < ds.row_off[bi + 1]; ++w)
+        std::copy(h_out.begin() + (size_t)u * P, h_out.begin() + (size_t)(u + 1) * P, ds.dosage + (size_t)ds.rows[w] * P);
+    }
+  }
+  return HMC_OK;
+}
+
+int Ctx::haplotype_dosages(int64_t n, const int32_t *indiv, int n_patterns, const int32_t *start, const int32_t *len, int maxlen,
+                           const int32_t *alleles_a, const int32_t *alleles_b, double *dosage, int32_t *status) {
+  if (!have_estep) return fail(HMC_EARG, "haplotype dosages need an E-step first (hmc_resolve_all)");
+  if (estep_gen != model_gen)
+    return fail(HMC_EARG, "haplotype dosages: the model changed since the last E-step (hmc_resolve_all again)");
+  if (pan.amax > 44) return fail(HMC_EUNSUPPORTED, "haplotype dosages with more than 44 alleles per locus");
+  const int nl = nloc(), L = pan.L, P = n_patterns;
+  if (!indiv) n = nl;
+  if (n < 0) return fail(HMC_EARG, "haplotype dosages: n = %lld is negative", (long long)n);
+  if (P < 0 || (P > 0 && (!start || !len || !alleles_a))) return fail(HMC_EARG, "haplotype dosages: no patterns given");
+  for (int64_t q = 0; indiv && q < n; ++q)
+    if (indiv[q] < i0 || indiv[q] >= i1)
+      return fail(HMC_EARG, "haplotype dosages: entry %lld: individual %d is outside this rank's shard [%d, %d)", (long long)q,
+                  indiv[q], i0, i1);
+  for (int p = 0; p < P; ++p)
+    if (start[p] < 0 || len[p] < 1 || len[p] > maxlen || (long long)start[p] + len[p] > L)
+      return fail(HMC_EARG, "haplotype dosages: pattern %d: window start %d, length %d is outside [0, %d) or longer than maxlen %d",
+                  p, start[p], len[p], L, maxlen);
+  ds_ms_struct = ds_ms_fb = ds_ms_sweep = 0;
+  ds_groups = ds_pruned = ds_spilled = ds_ns = ds_rounds = 0;
+  if (n == 0 || P == 0) return HMC_OK;
+  // symbols to allele-table indices, one byte each
+  std::vector<uint8_t> codes((size_t)P * 2 * maxlen, (uint8_t)DOSE_ANY);
+  for (int p = 0; p < P; ++p)
+    for (int side = 0; side < 2; ++side) {
+      const int32_t *row = side ? alleles_b : alleles_a;
+      if (!row) continue;  // (row B not given: any allele everywhere)
+      for (int q = 0; q < len[p]; ++q) {
+        const int32_t sy = row[(size_t)p * maxlen + q];
+        if (sy == -1) continue;
+        const auto &tab = pan.sym[start[p] + q];
+        uint8_t c = (uint8_t)DOSE_ABSENT;
+        for (size_t j = 0; j < tab.size(); ++j)
+          if (tab[j].first == sy) c = (uint8_t)j;
+        codes[((size_t)p * 2 + side) * maxlen + q] = c;
+      }
+    }
+  // NS: as asked, else the smallest of 1, 2, 4 that runs the call in one round, else 4: on cfg 2 the sweep measured
+  // faster at NS = 4 in twice the rounds than at NS = 8 (14.1-14.7 against 14.6-15.3 ms on windows stepping 8,
+  // 47.8-48.2 against 56.5-57.1 ms on windows stepping 2; profiles/haplotype_dosages/README.md)
+  DosePlan pl;
+  int NS = ds_slots;
+  if (NS == 0) {
+    dose_plan(P, start, len, head_len, DOSE_SLOTS_AUTO_MAX, pl);
+    NS = pl.need <= 1 ? 1 : pl.need <= 2 ? 2 : DOSE_SLOTS_AUTO_MAX;
+  }
+  if (NS != DOSE_SLOTS_AUTO_MAX || ds_slots) dose_plan(P, start, len, head_len, NS, pl);
+  ds_ns = ds_ns_run = NS;
+  ds_rounds = pl.rounds;
+  auto local = [&](int64_t q) { return indiv ? indiv[q] - i0 : (int)q; };
+  ds.P = P;
+  ds.maxlen = maxlen;
+  ds.n_events = (int)pl.ev.size();
+  ds.dosage = dosage;
+  ds.row_off.assign((size_t)nl + 1, 0);
+  for (int64_t q = 0; q < n; ++q) ++ds.row_off[local(q) + 1];
+  for (int i = 0; i < nl; ++i) ds.row_off[i + 1] += ds.row_off[i];
+  ds.rows.assign((size_t)n, 0);
+  {
+    std::vector<int64_t> at(ds.row_off.begin(), ds.row_off.end() - 1);
+    for (int64_t q = 0; q < n; ++q) ds.rows[at[local(q)]++] = q;
+  }
+  ds.status.assign(nl, 1);
+  if (dosage) std::fill(dosage, dosage + (size_t)n * P, 0.0);
+  hipError_t er;
+  if ((er = d_xstatus.ensure(nl)) || (er = d_xre.ensure(nl)) || (er = d_xfmax.ensure(nl)) || (er = d_ds_ev.ensure(pl.ev.size())) ||
+      (er = d_ds_codes.ensure(codes.size())) ||
+      (er = hipMemcpyAsync(d_ds_ev.p, pl.ev.data(), pl.ev.size() * sizeof(DoseEvent), hipMemcpyHostToDevice, st)) ||
+      (er = hipMemcpyAsync(d_ds_codes.p, codes.data(), codes.size(), hipMemcpyHostToDevice, st)) || (er = sync_st()))
+    return hipfail(er, "haplotype dosages");
+  // the pass counts in the genotype posteriors' fields: theirs are put back
+  const double g_struct = xp_ms_struct, g_fb = xp_ms_fb, g_sites = xp_ms_sites;
+  const int g_groups = xp_groups, g_pruned = xp_pruned;
+  std::vector<char> asked(nl, 0);  // the passes run over the individuals asked for, not the whole shard
+  for (int i = 0; i < nl; ++i) asked[i] = ds.row_off[i + 1] > ds.row_off[i];
+  const int rc = xp_pass(XP_DOSE, "haplotype dosages", &asked);
+  ds_ms_struct = xp_ms_struct;
+  ds_ms_fb = xp_ms_fb;
+  ds_ms_sweep = xp_ms_sites;
+  ds_groups = xp_groups;
+  ds_pruned = xp_pruned;
+  xp_ms_struct = g_struct;
+  xp_ms_fb = g_fb;
+  xp_ms_sites = g_sites;
+  xp_groups = g_groups;
+  xp_pruned = g_pruned;
+  ds.dosage = nullptr;
+  if (rc) return rc;
+  for (int64_t q = 0; q < n; ++q) {
+    const int stt = ds.status[local(q)];
+    if (status) status[q] = stt;
+    // (a restarted pass may have left an earlier attempt's numbers in a row that ended unresolved)
+    if (stt != 0 && dosage) std::fill(dosage + (size_t)q * P, dosage + (size_t)(q + 1) * P, 0.0);
+  }
+  return HMC_OK;
+}
+
 int Ctx::posterior_draws(int64_t n, const int32_t *indiv, int draws, uint64_t seed, int32_t *hap, double *prob, int32_t *status) {
   if (!have_estep) return fail(HMC_EARG, "posterior draws need an E-step first (hmc_resolve_all)");
   if (estep_gen != model_gen)
@@ -865,6 +1025,7 @@ int Ctx::xp_pass(XpMode mode, const char *what, const std::vector<char> *only) {
     xp_ms_fb = xp_ms_sites = 0;
     if (mode == XP_SWITCH) sw_spilled = 0;
     if (mode == XP_PAIR) pr_spilled = 0;
+    if (mode == XP_DOSE) ds_spilled = 0;
     rc = estep_split(order, true);
     if (rc != ESTEP_RESTART) break;
   }

@@ -1515,6 +1515,271 @@ hipError_t launch_exact_pair_posteriors(const ExactArgs &a, const PairArgs &s, i
                    : launch_pair<8>(a, s, grid, st, block);
 }
 
+// Haplotype dosages (hmc_haplotype_dosages): for caller-given patterns p — a
+// window start .. start + len - 1 with two rows of allele codes A, B (an allele
+// index, DOSE_ANY or DOSE_ABSENT) — d = sum over unordered pairs {h0, h1} of
+// post({h0, h1}) ([M(h0, h1)] + [M(h1, h0)]), M(x, y) true when x matches row A
+// and y row B at every locus of the window.  A sibling of
+// exact_pair_posteriors: one block per individual, a state t carries 2 NS
+// doubles g[slot][c][t], c = 0 when the haplotype held against row A lies on
+// t's a side (hdr & 0xFF), c = 1 when on its b side; a slot holds one pattern
+// from its first record to its last.  With xa, xb the state's alleles of locus
+// k: ok0 = match(xa, A[k]) && match(xb, B[k]), ok1 = match(xb, A[k]) &&
+// match(xa, B[k]).
+//   anchor    slot s at the record of `start` from fwd: g[s][0][t] = ok0 ?
+//             fwd[t] : 0, g[s][1][t] = ok1 ? fwd[t] : 0 (a homozygous matching
+//             state takes both);
+//   propagate record j from j - 1 as exact_switch_posteriors does — over t's
+//             contributions r in stored order g'[c ^ rev(r)][t] += g[c][state(r)]
+//             tpv[t], the first term assigns, later ones add — then a label
+//             whose ok is false at locus j - 1 is stored as 0.0; a slot with
+//             both false at t takes no sums.  Contribution words and tpv[t] are
+//             read once per state for all live slots;
+//   evaluate  at the record of the window's last locus: S_c = sum_t g[c][t]
+//             bwd[t]; wavefront 0 owns S_0, wavefront 1 S_1, lane l adds states
+//             l, l + 64, ... ascending, then the fixed butterfly; one thread
+//             forms d = (S_0 + S_1) / P(genotype) (scaled as in
+//             exact_site_posteriors).
+// Loci below head_len (head_len > 1) are matched at the head record from the
+// states' two head patterns, all of the window's head loci at the anchor, with
+// no propagation between them.
+// Why the lattice gives the definition (the path-to-pair bookkeeping of
+// hmc_posterior_draws): a path ends with its a-side and b-side haplotype, and
+// both labels are summed, so a path of posterior w adds w ([M(a, b)] + [M(b,
+// a)]).  A heterozygous head state carries its factor 2 and is the pair's only
+// path; a heterozygous pair behind a homozygous prefix is two paths of half
+// its posterior each, one per orientation, and both add the same two-term sum;
+// a homozygous pair is one path whose two labels coincide.  In every case the
+// pair adds post ([M(h0, h1)] + [M(h1, h0)]).
+// The host gives one event list for the call (DoseEvent, exact.hpp), the same
+// for every individual, in execution order: the kernel never searches the
+// patterns, propagates while a slot is live and jumps to the next event's
+// record when none is (also how a later round starts again).  A pattern's
+// double is a function of the records, the forward and backward values and its
+// own (start, len, A, B): the slot only names where its labelled values are
+// kept, so NS, slot, round, the other patterns, block size, grid, grouping,
+// shard and tier do not change the bits.  No floating-point atomics, no
+// cross-wave sums beyond S_0 + S_1.
+// The frontiers (32 NS bytes per state for the two) live in LDS when the
+// individual's largest record has at most `tier` states, else in the block's
+// slice of an HBM scratch: the same doubles in the same order.
+// EXT (ExactArgs::extended): as exact_switch_posteriors, every live slot's sums
+// times the record's forward exponent step; evaluation cancels E_j + G_j
+// against E_L.
+template <int NS, bool EXT>
+__global__ __launch_bounds__(256) void exact_haplotype_dosages(ExactArgs a, DoseArgs s) {
+  extern __shared__ __attribute__((aligned(16))) double ds_lds[];  // [2 frontiers][lds_states][NS slots][2 labels]
+  __shared__ int fmx;
+  __shared__ double s_sum[PAIR_SLOTS_MAX][2];  // S_0, S_1 of the evaluations not yet written out
+  __shared__ int s_col[PAIR_SLOTS_MAX];        // their patterns
+  const int tid = threadIdx.x, NT = blockDim.x;
+  const int lane = tid & (WAVE - 1), wave = tid / WAVE, nw = NT / WAVE;
+  const int L = a.L, hl = a.head_len, P = s.n_patterns, ML = s.maxlen;
+  for (int q = blockIdx.x; q < a.n_order; q += gridDim.x) {
+    const int bi = a.order[q];
+    double *out = s.dosage + (size_t)q * P;
+    const int st0 = a.status[bi];
+    const double pg = EXT ? a.xtot[bi] : a.gprob[bi];
+    const bool resolved = (st0 == EST_OK || st0 == EST_OK_PRUNED) && pg > 0.0 && !isinf(pg);
+    const unsigned long long *roff = a.rec_off + (size_t)bi * (L + 1);
+    const unsigned long long *xo = a.x_off + (size_t)bi * (L + 1);
+    // the individual's largest record (block-uniform after the barrier)
+    int fbig = 0;
+    if (resolved) {
+      __syncthreads();  // every thread has read the previous individual's maximum
+      if (tid == 0) fmx = 0;
+      __syncthreads();
+      int f = 0;
+      for (int j = hl + tid; j <= L; j += NT) f = max(f, (int)a.rec[roff[j]]);
+      atomicMax(&fmx, f);
+      __syncthreads();
+      fbig = fmx;
+    }
+    const bool in_lds = fbig <= s.tier && fbig <= s.lds_states;
+    // (a frontier neither store holds cannot occur: the host sizes the scratch from the group's fmax)
+    const bool fits = in_lds || (s.scratch && fbig <= s.scratch_states);
+    if (!resolved || (!EXT && pg < SITE_PG_MIN) || !fits) {  // a row of zeros: unresolved (1), or P(genotype) subnormal (2)
+      for (int i = tid; i < P; i += NT) out[i] = 0.0;
+      if (tid == 0) s.status[q] = resolved && fits ? 2 : 1;
+      continue;
+    }
+    const size_t cap = in_lds ? (size_t)s.lds_states : (size_t)s.scratch_states;
+    double *cur = in_lds ? ds_lds : s.scratch + (size_t)blockIdx.x * 4 * NS * cap;
+    double *prev = cur + 2 * NS * cap;
+    int sc = EXT ? 0 : -ilogb(pg), sa = sc / 2, sb = sc - sa;
+    const double pgs = EXT ? pg : ldexp(pg, sc);
+    const int EL = EXT ? a.xtot_exp[bi] : 0;
+    // the exponents exact_fb left with record j (EXT): E_j, G_j
+    auto rec_exp = [&](int j) { return (const int32_t *)(a.x + xo[j] + 4ull * a.rec[roff[j]]); };
+    auto match = [](uint32_t x, uint32_t code) { return code == DOSE_ANY || code == x; };
+    __syncthreads();  // the previous individual's last readers of the frontiers are done
+    unsigned live = 0;   // slots that hold a pattern (block-uniform, as everything the events decide)
+    unsigned pend = 0;   // slots whose S_0, S_1 wait in s_sum
+    int j = hl;          // the record `cur` belongs to
+    long long cbase[NS]; // per slot: the pattern's row A in s.codes, less its start (row B: + maxlen)
+#pragma unroll
+    for (int u = 0; u < NS; ++u) cbase[u] = 0;
+    // the sums of the evaluations since the last barrier, one thread per slot (after a barrier)
+    auto flush = [&]() {
+      if (tid < NS && ((pend >> tid) & 1u)) out[s_col[tid]] = (s_sum[tid][0] + s_sum[tid][1]) / pgs;
+      pend = 0u;
+    };
+    for (int e = 0; e < s.n_events; ++e) {
+      const DoseEvent ev = s.ev[e];
+      const int kind = ev.op & 3, slot = ev.op >> 2;
+      if (ev.rec < hl || ev.rec > L || slot < 0 || slot >= NS || ev.pat < 0 || ev.pat >= P || ev.start < 0 ||
+          ev.start >= L)
+        continue;  // (the host builds none such)
+      if (live == 0u || ev.rec < j) {  // nothing to carry: the next round, or a gap between windows
+        j = ev.rec;
+        live = 0u;
+      }
+      while (j < ev.rec) {  // record j + 1 from record j (j + 1 > head_len: never the head record)
+        if (pend) {
+          __syncthreads();
+          flush();
+        }
+        ++j;
+        double *x = prev;
+        prev = cur;
+        cur = x;
+        const RecView R(a.rec + roff[j], false);
+        const int step = EXT ? rec_exp(j)[0] - rec_exp(j - 1)[0] : 0;
+        uint32_t ca[NS], cb[NS];  // the live slots' codes of locus j - 1
+#pragma unroll
+        for (int u = 0; u < NS; ++u) {
+          const bool on = (live >> u) & 1u;
+          ca[u] = on ? s.codes[cbase[u] + (j - 1)] : DOSE_ABSENT;
+          cb[u] = on ? s.codes[cbase[u] + ML + (j - 1)] : DOSE_ABSENT;
+        }
+        for (int t = tid; t < R.F; t += NT) {
+          const uint32_t h = R.hdr[t], xa = h & 0xFFu, xb = (h >> 8) & 0xFFu;
+          unsigned k0 = 0u, k1 = 0u;  // per slot: ok0, ok1
+#pragma unroll
+          for (int u = 0; u < NS; ++u)
+            if ((live >> u) & 1u) {
+              if (match(xa, ca[u]) && match(xb, cb[u])) k0 |= 1u << u;
+              if (match(xb, ca[u]) && match(xa, cb[u])) k1 |= 1u << u;
+            }
+          const unsigned need = k0 | k1;
+          double n0[NS], n1[NS];
+#pragma unroll
+          for (int u = 0; u < NS; ++u) n0[u] = n1[u] = 0.0;
+          if (need) {
+            const double tpv = R.tpv[t];
+            const uint32_t r0 = R.cb[t], r1 = R.cb[t + 1];
+            for (uint32_t r = r0; r < r1; ++r) {
+              const uint32_t w = R.ct[r];
+              const bool rv = cw_rev(w);
+              const double2 *p = (const double2 *)(prev + (size_t)cw_state(w) * 2 * NS);
+#pragma unroll
+              for (int u = 0; u < NS; ++u)
+                if ((need >> u) & 1u) {
+                  const double2 g = p[u];
+                  const double v0 = (rv ? g.y : g.x) * tpv, v1 = (rv ? g.x : g.y) * tpv;
+                  n0[u] = r == r0 ? v0 : n0[u] + v0;
+                  n1[u] = r == r0 ? v1 : n1[u] + v1;
+                }
+            }
+          }
+          double2 *o = (double2 *)(cur + (size_t)t * 2 * NS);
+#pragma unroll
+          for (int u = 0; u < NS; ++u)
+            if ((live >> u) & 1u) {
+              const double g0 = (k0 >> u) & 1u ? (EXT ? ldexp(n0[u], step) : n0[u]) : 0.0;
+              const double g1 = (k1 >> u) & 1u ? (EXT ? ldexp(n1[u], step) : n1[u]) : 0.0;
+              o[u] = make_double2(g0, g1);
+            }
+        }
+        __syncthreads();
+      }
+      const RecView R(a.rec + roff[j], j == hl);
+      if (kind == DOSE_EV_EVAL) {
+        if (!((live >> slot) & 1u)) continue;  // (none such)
+        const double *bw = (const double *)(a.x + xo[j]) + R.F;
+        if constexpr (EXT) {
+          sc = EL - rec_exp(j)[0] - rec_exp(j)[1];
+          sa = sc / 2;
+          sb = sc - sa;
+        }
+        for (int w = wave; w < 2; w += nw) {  // wave-uniform: S_0, S_1
+          double part[1] = {0.0};
+          for (int t = lane; t < R.F; t += WAVE) part[0] += ldexp(cur[((size_t)t * NS + slot) * 2 + w], sa) * ldexp(bw[t], sb);
+          const double v = group_sum_fixed<WAVE>(part);
+          if (lane == 0) {
+            s_sum[slot][w] = v;
+            if (w == 0) s_col[slot] = ev.pat;
+          }
+        }
+        pend |= 1u << slot;
+        live &= ~(1u << slot);
+      } else if (kind == DOSE_EV_ANCHOR) {
+        if (pend) {  // (the barrier also lets the sums finish reading the slot this anchor overwrites)
+          __syncthreads();
+          flush();
+        }
+        const long long base = (long long)ev.pat * 2 * ML - ev.start;
+#pragma unroll
+        for (int u = 0; u < NS; ++u)
+          if (u == slot) cbase[u] = base;
+        const double *fw = (const double *)(a.x + xo[j]);
+        const bool head = j == hl && hl > 1;  // the window's loci below head_len, from the head patterns
+        const int k0 = ev.start, k1 = head ? min(ev.start + ev.len, hl) : ev.start + 1;
+        const uint32_t *plo = R.cb + R.F + 1, *phi = plo + R.F;
+        for (int t = tid; t < R.F; t += NT) {
+          bool ok0 = true, ok1 = true;
+          for (int k = k0; k < k1; ++k) {
+            uint32_t xa, xb;
+            if (head) {
+              xa = a.head_al[(size_t)plo[t] * hl + k];
+              xb = a.head_al[(size_t)phi[t] * hl + k];
+            } else {
+              const uint32_t h = R.hdr[t];
+              xa = h & 0xFFu;
+              xb = (h >> 8) & 0xFFu;
+            }
+            const uint32_t cA = s.codes[base + k], cB = s.codes[base + ML + k];
+            ok0 = ok0 && match(xa, cA) && match(xb, cB);
+            ok1 = ok1 && match(xb, cA) && match(xa, cB);
+          }
+          const double f = fw[t];
+          double *g = cur + ((size_t)t * NS + slot) * 2;
+          g[0] = ok0 ? f : 0.0;
+          g[1] = ok1 ? f : 0.0;
+        }
+        __syncthreads();
+        live |= 1u << slot;
+      }
+    }
+    if (pend) {
+      __syncthreads();
+      flush();
+    }
+    if (tid == 0) s.status[q] = 0;
+  }
+}
+
+template <int NS>
+static hipError_t launch_dosage(const ExactArgs &a, const DoseArgs &s, int grid, hipStream_t st, int block) {
+  if (a.extended)
+    hipLaunchKernelGGL((exact_haplotype_dosages<NS, true>), dim3(grid), dim3(block), (size_t)s.lds_states * 32 * NS, st, a, s);
+  else
+    hipLaunchKernelGGL((exact_haplotype_dosages<NS, false>), dim3(grid), dim3(block), (size_t)s.lds_states * 32 * NS, st, a, s);
+  return hipGetLastError();
+}
+
+hipError_t launch_exact_haplotype_dosages(const ExactArgs &a, const DoseArgs &s, int ns, int grid, hipStream_t st, int block) {
+  if (a.n_order <= 0 || s.n_events <= 0) return hipSuccess;
+  if (block < WAVE || block > 256 || block % WAVE || grid < 1 || !pair_slots_ok(ns) || s.tier < 1 || s.lds_states < 1 ||
+      s.lds_states > pair_tier_max(ns) || !s.ev || !s.codes || !s.dosage || !s.status || s.n_patterns < 1 || s.maxlen < 1 ||
+      (s.scratch && s.scratch_states < 1))
+    return hipErrorInvalidValue;
+  return ns == 1   ? launch_dosage<1>(a, s, grid, st, block)
+         : ns == 2 ? launch_dosage<2>(a, s, grid, st, block)
+         : ns == 4 ? launch_dosage<4>(a, s, grid, st, block)
+                   : launch_dosage<8>(a, s, grid, st, block);
+}
+
 // Posterior draws (hmc_posterior_draws): whole haplotype pairs sampled from
 // the exact posterior by backward sampling through the forward values of
 // exact_fb.  A state's forward value is tpv[t] times the sum of its

@@ -1,5 +1,6 @@
 // exact.hpp — device arguments of the exact M-step kernels (exact.hip).
 #pragma once
+#include "dosage_plan.hpp"
 #include "hmc_internal.hpp"
 
 namespace hmc {
@@ -171,6 +172,30 @@ constexpr int pair_tier_max(int ns) { return 65024 / (32 * ns); }  // 2032, 1016
 constexpr int PAIR_TIER_DEFAULT = pair_tier_max(PAIR_SLOTS_MAX);
 // after exact_fb over the same group; NS, block sizes 64 .. 256 and the grid do not change the bits
 hipError_t launch_exact_pair_posteriors(const ExactArgs &a, const PairArgs &s, int ns, int grid, hipStream_t st, int block = 256);
+
+// Haplotype dosages (exact_haplotype_dosages): expected copies of caller-given
+// patterns.  The pattern set, and so the plan (dosage_plan.hpp), is the same
+// for every individual of a call: codes[pattern][row A, row B][maxlen] bytes
+// (an allele-table index of the locus, DOSE_ANY or DOSE_ABSENT: both above 43,
+// the largest index the exact path supports) and one event list in execution
+// order (DoseEvent).  Individual q of the group (ExactArgs::order) owns output
+// row q.
+struct DoseArgs {
+  const DoseEvent *ev = nullptr;
+  int n_events = 0;
+  const uint8_t *codes = nullptr;                // [n_patterns][2][maxlen]
+  int n_patterns = 0, maxlen = 0;
+  double *dosage = nullptr;                      // [n_order][n_patterns]
+  int32_t *status = nullptr;                     // [n_order] 0 ok; rows of zeros: 1 unresolved, 2 P(genotype) subnormal
+  int tier = 0;                                  // as PairArgs
+  int lds_states = 0;
+  double *scratch = nullptr;                     // [grid][4 NS scratch_states]
+  int scratch_states = 0;
+};
+constexpr int DOSE_SLOTS_AUTO_MAX = 4;  // the most slots the automatic schedule takes (8 only when asked for: measured slower)
+// after exact_fb over the same group; NS (1, 2, 4, 8; tiers as pair_tier_max), block sizes 64 .. 256 and the grid do
+// not change the bits
+hipError_t launch_exact_haplotype_dosages(const ExactArgs &a, const DoseArgs &s, int ns, int grid, hipStream_t st, int block = 256);
 
 // Posterior draws (exact_posterior_draws): `draws` lattice paths per
 // individual of the group, sampled backwards through the forward values

@@ -603,6 +603,78 @@ class HaploModel:
         """pair_posteriors of pair_span_list(span) as text, one line per query of status 0 (hmc_write_pair_posteriors)."""
         self._check(lib().hmc_write_pair_posteriors(self._h, path.encode(), int(span)))
 
+    @staticmethod
+    def _dosage_patterns(start, alleles_a, alleles_b):
+        """Ragged pattern rows padded to maxlen: start[P], len[P], maxlen, A[P][maxlen], B or None."""
+        st = np.ascontiguousarray(start, np.int32).reshape(-1)
+        rows_a = [np.asarray(r, np.int64).reshape(-1) for r in alleles_a]
+        if len(rows_a) != len(st):
+            raise ValueError("start and alleles_a differ in length")
+        ln = np.array([len(r) for r in rows_a], np.int32)
+        maxlen = max(1, int(ln.max())) if len(ln) else 1
+        A = np.full((len(st), maxlen), -1, np.int32)
+        for p, r in enumerate(rows_a):
+            A[p, :len(r)] = r
+        B = None
+        if alleles_b is not None:
+            rows_b = [np.asarray(r, np.int64).reshape(-1) for r in alleles_b]
+            if [len(r) for r in rows_b] != ln.tolist():
+                raise ValueError("alleles_a and alleles_b differ in shape")
+            B = np.full((len(st), maxlen), -1, np.int32)
+            for p, r in enumerate(rows_b):
+                B[p, :len(r)] = r
+        return st, ln, maxlen, A, B
+
+    def haplotype_dosages(self, start, alleles_a, alleles_b=None, indiv=None) -> dict:
+        """Exact expected copies of caller-given haplotypes under the model of
+        the last resolve_all (hmc_haplotype_dosages).  Pattern p is the window
+        start[p] .. start[p] + len(alleles_a[p]) - 1 with allele symbols
+        alleles_a[p] (ragged lists are padded; -1 = any allele) and, if given,
+        alleles_b[p] of the same length for the other haplotype.  For the
+        panel indices `indiv` (None = this rank's whole shard) dosage[n, P] =
+        sum over pairs {h0, h1} of post({h0, h1}) ([h0 matches A and h1 B] +
+        [h1 matches A and h0 B]): with alleles_b None the number of the
+        individual's two haplotypes that carry A, in [0, 2]; status[n] (0 ok;
+        rows of zeros: 1 individual unresolved, 2 its P(genotype) subnormal)."""
+        st, ln, maxlen, A, B = self._dosage_patterns(start, alleles_a, alleles_b)
+        if indiv is None:
+            qi, n = None, self.i1 - self.i0
+        else:
+            qi = np.ascontiguousarray(indiv, np.int32).reshape(-1)
+            n = len(qi)
+        P = len(st)
+        out = dict(dosage=np.zeros((n, P), np.float64), status=np.zeros(n, np.int32))
+        self._check(lib().hmc_haplotype_dosages(self._h, n, None if qi is None else _p(qi, C.c_int32), P, _p(st, C.c_int32),
+                                                _p(ln, C.c_int32), maxlen, _p(A, C.c_int32),
+                                                None if B is None else _p(B, C.c_int32), _p(out["dosage"], C.c_double),
+                                                _p(out["status"], C.c_int32)))
+        return out
+
+    def dosage_stats(self) -> dict:
+        """Device ms and counts of the last haplotype_dosages (hmc_last_dosage_stats)."""
+        s, f, k = C.c_double(), C.c_double(), C.c_double()
+        g, p, sp, ns, r = C.c_int(), C.c_int(), C.c_int(), C.c_int(), C.c_int()
+        self._check(lib().hmc_last_dosage_stats(self._h, C.byref(s), C.byref(f), C.byref(k), C.byref(g), C.byref(p),
+                                                C.byref(sp), C.byref(ns), C.byref(r)))
+        return dict(structure_ms=s.value, fb_ms=f.value, sweep_ms=k.value, groups=g.value, n_pruned=p.value,
+                    n_spilled=sp.value, slots=ns.value, rounds=r.value)
+
+    def set_dosage_tuning(self, slots: int = 0, tier: int = 0):
+        """Patterns a state carries at once in the dosage sweep (1, 2, 4 or 8)
+        and states per locus it keeps in LDS; 0 = automatic for each.  Results
+        do not depend on it."""
+        self._check(lib().hmc_set_dosage_tuning(self._h, int(slots), int(tier)))
+
+    def write_haplotype_dosages(self, path: str, names, start, alleles_a, alleles_b=None):
+        """haplotype_dosages of the whole shard as text, one line per individual of status 0 and pattern
+        (hmc_write_haplotype_dosages)."""
+        st, ln, maxlen, A, B = self._dosage_patterns(start, alleles_a, alleles_b)
+        if len(names) != len(st):
+            raise ValueError("names and start differ in length")
+        arr = (C.c_char_p * max(1, len(st)))(*[str(x).encode() for x in names])
+        self._check(lib().hmc_write_haplotype_dosages(self._h, path.encode(), len(st), arr, _p(st, C.c_int32), _p(ln, C.c_int32),
+                                                      maxlen, _p(A, C.c_int32), None if B is None else _p(B, C.c_int32)))
+
     def posterior_draws(self, draws: int, seed: int, indiv=None) -> dict:
         """Whole haplotype pairs sampled from the exact posterior under the
         model of the last resolve_all (hmc_posterior_draws): for the panel

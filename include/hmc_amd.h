@@ -354,6 +354,65 @@ int hmc_pair_span_list(hmc_ctx *ctx, int span, int64_t *n, int32_t *indiv, int32
  * individual took.  Replaces no reference interface. */
 int hmc_last_pair_stats(const hmc_ctx *ctx, double *structure_ms, double *fb_ms, double *sweep_ms, int *groups, int *n_pruned,
                         int *n_spilled, int *slots, int *max_rounds);
+/* Haplotype dosages: the exact expected number of copies of caller-given
+ * haplotypes an individual carries, under the model of the last E-step — what
+ * haplotype association and haplotype-frequency estimates need (the column
+ * mean over individuals, halved, is the population haplotype frequency).
+ * A pattern p is the window start[p] .. start[p] + len[p] - 1 with two rows of
+ * allele symbols, alleles_a[p][k] and alleles_b[p][k] (k < len[p]; arrays of
+ * [n_patterns][maxlen], entries past len[p] ignored); -1 in a row means "any
+ * allele"; alleles_b = NULL means all -1.  For haplotypes x, y let M_p(x, y)
+ * be true when at every locus k of the window A[k] is -1 or equals x[k] and
+ * B[k] is -1 or equals y[k].  With post({h0, h1}) the exact posterior over
+ * unordered pairs (the one hmc_posterior_draws samples):
+ *     d[i][p] = sum over pairs {h0, h1} of post({h0, h1}) ([M_p(h0, h1)] + [M_p(h1, h0)])
+ * — always two terms, also when h0 = h1.  Consequences:
+ *   B all -1 (one-sided): d is the expected number of the individual's two
+ *     haplotypes that carry A on the window, the haplotype dosage, in [0, 2];
+ *     a homozygous carrier has 2.
+ *   Some locus where A and B are both given and differ: no pair matches in
+ *     both orientations, so d is the posterior probability of the
+ *     configuration, in [0, 1].  Two heterozygous loci with -1 between them
+ *     give cis or trans; every locus given is the posterior of that whole pair
+ *     (a read-backed phase set, another tool's phasing, the truth set).
+ *   A and B both all -1: d = 2 up to rounding (allowed: a normalisation check).
+ *   A symbol the locus's allele table does not hold matches nothing: d is
+ *     exactly 0.0, no error (scans include absent haplotypes).
+ * The sum runs over the lattice states exactly, by a labelled forward sweep
+ * that filters by the pattern at every locus of its window: a path adds its
+ * posterior once for each orientation in which its two haplotypes match, and
+ * by the path-to-pair bookkeeping stated under hmc_posterior_draws (a
+ * heterozygous head state carries its factor 2, a heterozygous pair behind a
+ * homozygous prefix is two paths of half each, a homozygous pair is one path)
+ * the paths of a pair add exactly the two-term sum above.
+ * indiv[n] are panel indices inside this rank's shard, in any order, repeats
+ * allowed; indiv = NULL means the whole shard (n is ignored).  Outputs, either
+ * of which may be NULL: dosage[n][n_patterns], status[n]; status 0 / 1 / 2 as
+ * for hmc_switch_posteriors, rows of status 1 and 2 are zeros.  For an
+ * individual with a missing allele at a head locus, loci below head_len come
+ * from the reference's head pairing, which is not a phasing model: for a
+ * window that touches them only the normalisation holds.
+ * n = 0 or n_patterns = 0 is HMC_OK with no device work.  HMC_EARG, with a
+ * message naming the first offender, for an individual outside this rank's
+ * shard and for a pattern with start < 0, len < 1, len > maxlen or start + len
+ * > L; HMC_EARG when no E-step has run or the model has changed since the last
+ * one; HMC_EUNSUPPORTED as for hmc_genotype_posteriors.  Runs its own
+ * forward-backward pass, over the individuals asked for only, and changes no
+ * later result; the rows go through the device in batches of at most 512 MiB.
+ * The bits of d[i][p] depend on the model, the range setting
+ * (hmc_set_posterior_range), i and p's own (start, len, A, B) alone: not on
+ * the other patterns or their order, the other individuals, the slots, rounds
+ * and tier of hmc_set_dosage_tuning, launch shapes, store budgets, groups or
+ * sharding.  Replaces no reference interface. */
+int hmc_haplotype_dosages(hmc_ctx *ctx, int64_t n, const int32_t *indiv, int n_patterns, const int32_t *start,
+                          const int32_t *len, int maxlen, const int32_t *alleles_a, const int32_t *alleles_b, double *dosage,
+                          int32_t *status);
+/* Last hmc_haplotype_dosages: as hmc_last_pair_stats; rounds: the sweeps over
+ * the records the call's plan took (more than one when more windows overlap
+ * than the sweep has slots).  All zero after a call with n = 0 or
+ * n_patterns = 0.  Replaces no reference interface. */
+int hmc_last_dosage_stats(const hmc_ctx *ctx, double *structure_ms, double *fb_ms, double *sweep_ms, int *groups, int *n_pruned,
+                          int *n_spilled, int *slots, int *rounds);
 /* Posterior draws: whole haplotype pairs sampled from the exact posterior
  * P(pair | genotype) under the model of the last E-step — what multiple
  * imputation and the posterior of any statistic that is no one- or two-locus
@@ -590,6 +649,16 @@ int hmc_write_pair_posteriors(hmc_ctx *ctx, const char *path, int span);
  * separated by single spaces.  Needs a preceding hmc_resolve_all or hmc_run;
  * HMC_EARG for draws < 1.  Replaces no reference interface. */
 int hmc_write_posterior_draws(hmc_ctx *ctx, const char *path, int draws, uint64_t seed);
+/* hmc_haplotype_dosages of the whole shard as text (hmc_resolve
+ * --output-dosages FILE --haplotypes HAPFILE): the header
+ * "Id\tHaplotype\tDosage", then one line per individual of status 0 and per
+ * pattern, individual-major: the individual's id, names[p], the dosage as
+ * %.17g (reads back to the same double).  Patterns as for
+ * hmc_haplotype_dosages, with the same errors.  Needs a preceding
+ * hmc_resolve_all or hmc_run.  Replaces no reference interface. */
+int hmc_write_haplotype_dosages(hmc_ctx *ctx, const char *path, int n_patterns, const char *const *names,
+                                const int32_t *start, const int32_t *len, int maxlen, const int32_t *alleles_a,
+                                const int32_t *alleles_b);
 /* ---- tuning -------------------------------------------------------------- */
 /* frontier_cap: initial states per locus and individual (doubles on
  * overflow, at most 2 097 151); trace_bytes: trace-store budget (0 =
@@ -637,6 +706,15 @@ int hmc_set_switch_tier(hmc_ctx *ctx, int states);
  * depend on it.
  * Replaces no reference interface. */
 int hmc_set_pair_tuning(hmc_ctx *ctx, int slots, int tier_states);
+/* Schedule of hmc_haplotype_dosages, 0 = automatic for each, as
+ * hmc_set_pair_tuning.  slots: patterns a state carries at once (NS: 1, 2, 4 or
+ * 8; automatic: the smallest of 1, 2, 4 that runs the call in one round, else
+ * 4, which measured faster in twice the rounds than 8 does in half of them).
+ * tier_states: states per locus whose frontiers the sweep keeps in LDS (32 NS
+ * bytes per state; automatic: 254).  HMC_EARG for a slot count that is not
+ * instantiated or a tier above 254.  Results do not depend on it.
+ * Replaces no reference interface. */
+int hmc_set_dosage_tuning(hmc_ctx *ctx, int slots, int tier_states);
 /* E-step implementation: 0 (default) = two passes, a structure pass that
  * replays extendAll/addHaploPair (HaploBuilder.cpp:226-261) on pattern ids
  * and a value pass with the k-best lists; individuals whose forward

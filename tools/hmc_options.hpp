@@ -22,7 +22,9 @@ struct Options {
   int draws = 100;                     // --draws D (>= 1)
   unsigned long long seed = 0;         // --seed S
   bool have_draws = false, have_seed = false;
-  bool extended_range = false;         // --extended-range (needs one of the --output-*posteriors / --output-draws options)
+  std::string output_dosages;          // --output-dosages FILE
+  std::string haplotypes;              // --haplotypes HAPFILE (required with it)
+  bool extended_range = false;         // --extended-range (needs one of the --output-*posteriors / --output-draws / --output-dosages options)
 };
 
 // --output-posteriors (no reference counterpart): <first file>.posteriors, the
@@ -54,7 +56,10 @@ constexpr const char *USAGE =
     "  --output-draws FILE [--draws D] [--seed S]  write FILE: D haplotype pairs per individual drawn\n"
     "                        from the exact posterior under the final model, each with its posterior\n"
     "                        (default D = 100, S = 0; a draw depends on S, the individual and its index)\n"
-    "  --extended-range      the four options above in extended range: individuals whose likelihood\n"
+    "  --output-dosages FILE --haplotypes HAPFILE  write FILE: for every individual the exact expected\n"
+    "                        copies of each haplotype of HAPFILE (lines: name start a a a ... [| b b b ...],\n"
+    "                        start the 0-based first locus, alleles as the genotype files spell them, ? = any)\n"
+    "  --extended-range      the five options above in extended range: individuals whose likelihood\n"
     "                        underflows a double (panels of more than about 1 200 loci) get lines too";
 
 // 0 on success; otherwise `err` says what is wrong (a missing value, an
@@ -88,6 +93,8 @@ inline int parse_options(int argc, const char *const *argv, Options &o, std::str
     else if (a == "--pair-span") { if (!next()) return 1; o.pair_span = atoi(v); o.have_pair_span = true; }
     else if (a == "--output-draws") { if (!next()) return 1; o.output_draws = v; }
     else if (a == "--draws") { if (!next()) return 1; o.draws = atoi(v); o.have_draws = true; }
+    else if (a == "--output-dosages") { if (!next()) return 1; o.output_dosages = v; }
+    else if (a == "--haplotypes") { if (!next()) return 1; o.haplotypes = v; }
     else if (a == "--extended-range") o.extended_range = true;
     else if (a == "--seed") { if (!next()) return 1; o.seed = strtoull(v, nullptr, 10); o.have_seed = true; }
     else if (a == "-m" || a == "--model") { if (!next()) return 1; o.model = v; }          // HMC.cpp:35
@@ -116,9 +123,13 @@ inline int parse_options(int argc, const char *const *argv, Options &o, std::str
     err = "--draws and --seed need --output-draws FILE\n" + std::string(USAGE);
     return 1;
   }
+  if (o.output_dosages.empty() != o.haplotypes.empty()) {
+    err = "--output-dosages FILE and --haplotypes HAPFILE need each other\n" + std::string(USAGE);
+    return 1;
+  }
   if (o.extended_range && !o.output_posteriors && !o.output_switch_posteriors && o.output_pair_posteriors.empty() &&
-      o.output_draws.empty()) {
-    err = "--extended-range needs --output-posteriors, --output-switch-posteriors, --output-pair-posteriors or --output-draws\n" +
+      o.output_draws.empty() && o.output_dosages.empty()) {
+    err = "--extended-range needs --output-posteriors, --output-switch-posteriors, --output-pair-posteriors, --output-draws or --output-dosages\n" +
           std::string(USAGE);
     return 1;
   }

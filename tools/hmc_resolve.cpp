@@ -12,7 +12,8 @@
 //               [--sample-size 10] [--min-pattern-len 1] [--max-pattern-len 30]
 //               [--output-patterns x] [--output-posteriors] [--output-switch-posteriors]
 //               [--output-pair-posteriors FILE --pair-span K]
-//               [--output-draws FILE [--draws 100] [--seed 0]] [--extended-range] [--device 0] datafile ...
+//               [--output-draws FILE [--draws 100] [--seed 0]]
+//               [--output-dosages FILE --haplotypes HAPFILE] [--extended-range] [--device 0] datafile ...
 // --output-posteriors (no reference counterpart) writes <first file>.posteriors:
 // genotype posteriors at the loci with a missing input allele, under the final
 // model (hmc_write_posteriors).  --output-switch-posteriors (none either)
@@ -24,16 +25,21 @@
 // --output-draws FILE [--draws D] [--seed S] (none either) writes FILE: D
 // haplotype pairs per individual drawn from the exact posterior under the
 // final model, each with its posterior (hmc_write_posterior_draws).
-// --extended-range (none either) runs those four in extended range
+// --output-dosages FILE --haplotypes HAPFILE (none either) writes FILE: for
+// every individual the exact expected copies of each haplotype listed in
+// HAPFILE (hmc_hapfile.hpp; hmc_write_haplotype_dosages).
+// --extended-range (none either) runs those five in extended range
 // (hmc_set_posterior_range): individuals whose likelihood underflows a double
 // get lines too.
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <fstream>
 #include <string>
 #include <vector>
 
 #include "../include/hmc_amd.h"
+#include "hmc_hapfile.hpp"
 #include "hmc_options.hpp"
 
 int main(int argc, char **argv) {
@@ -68,6 +74,24 @@ int main(int argc, char **argv) {
   int N = 0, L = 0, A = 0;
   hmc_panel_info(ctx, &N, &L, &A);
   printf("Succesfully read Haplotype file with %d markers and %d genotypes.\n", L, N);
+  hmc_cli::HapList haps;
+  if (!o.haplotypes.empty()) {  // read before the run: a malformed list fails at once
+    std::string types((size_t)L + 1, '\0'), herr;
+    if ((rc = hmc_parse_files(format.c_str(), names.data(), (int)names.size(), nullptr, nullptr, nullptr, &types[0], nullptr)))
+      die("hmc_parse_files");
+    types.resize((size_t)L);
+    std::ifstream hf(o.haplotypes);
+    if (!hf) {
+      fprintf(stderr, "Can not open file %s!\n", o.haplotypes.c_str());
+      hmc_ctx_destroy(ctx);
+      return 1;
+    }
+    if (hmc_cli::parse_hapfile(hf, types, haps, herr)) {
+      fprintf(stderr, "%s\n", herr.c_str());
+      hmc_ctx_destroy(ctx);
+      return 1;
+    }
+  }
   hmc_iter_log log[256];
   int iters = 0, np0 = 0;
   double t_m0 = 0;
@@ -107,6 +131,14 @@ int main(int argc, char **argv) {
   }
   if (!o.output_draws.empty()) {  // of the same E-step
     if ((rc = hmc_write_posterior_draws(ctx, o.output_draws.c_str(), o.draws, o.seed))) die("hmc_write_posterior_draws");
+  }
+  if (!o.output_dosages.empty()) {  // of the same E-step
+    std::vector<const char *> hn;
+    for (auto &x : haps.names) hn.push_back(x.c_str());
+    const std::vector<int32_t> ha = haps.padded(false), hb = haps.padded(true);
+    if ((rc = hmc_write_haplotype_dosages(ctx, o.output_dosages.c_str(), (int)hn.size(), hn.data(), haps.start.data(),
+                                          haps.len.data(), haps.maxlen, ha.data(), haps.two_sided ? hb.data() : nullptr)))
+      die("hmc_write_haplotype_dosages");
   }
   hmc_ctx_destroy(ctx);
   return 0;
