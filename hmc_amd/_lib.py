@@ -98,6 +98,9 @@ _SIGS = [
                                          _P(C.c_int32)]),
     ("hmc_posterior_draws", _i, [_vp, C.c_int64, _P(C.c_int32), _i, _u64, _P(C.c_int32), _P(_d), _P(C.c_int32)]),
     ("hmc_last_draw_stats", _i, [_vp, _P(_d), _P(_d), _P(_d), _P(_i), _P(_i)]),
+    ("hmc_map_phase", _i, [_vp, C.c_int64, _P(C.c_int32), _P(C.c_int32), _P(_d), _P(C.c_int32)]),
+    ("hmc_last_map_stats", _i, [_vp, _P(_d), _P(_d), _P(_d), _P(_i), _P(_i)]),
+    ("hmc_write_map_phase", _i, [_vp, _cp]),
     ("hmc_set_posterior_range", _i, [_vp, _i]),
     ("hmc_genotype_likelihoods", _i, [_vp, C.c_int64, _P(C.c_int32), _P(_d), _P(C.c_int32), _P(C.c_int32)]),
     ("hmc_last_likelihood_stats", _i, [_vp, _P(_d), _P(_d), _P(_i)]),

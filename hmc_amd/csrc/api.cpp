@@ -1062,6 +1062,23 @@ int hmc_last_draw_stats(const hmc_ctx *h, double *structure_ms, double *fb_ms, d
   return HMC_OK;
 }
 
+int hmc_map_phase(hmc_ctx *h, int64_t n, const int32_t *indiv, int32_t *hap, double *prob, int32_t *status) {
+  if (!h) return HMC_EARG;
+  Ctx &c = h->c;
+  if (!c.have_panel) return c.fail(HMC_EARG, "no panel loaded");
+  return c.map_phase(n, indiv, hap, prob, status);
+}
+
+int hmc_last_map_stats(const hmc_ctx *h, double *structure_ms, double *fb_ms, double *sweep_ms, int *groups, int *n_pruned) {
+  if (!h) return HMC_EARG;
+  if (structure_ms) *structure_ms = h->c.mp_ms_struct;
+  if (fb_ms) *fb_ms = h->c.mp_ms_fb;
+  if (sweep_ms) *sweep_ms = h->c.mp_ms_sweep;
+  if (groups) *groups = h->c.mp_groups;
+  if (n_pruned) *n_pruned = h->c.mp_pruned;
+  return HMC_OK;
+}
+
 // Test seam of hmc_posterior_draws (not in the public header; results do not
 // depend on it): lds_chunks = final records of at most this many chunks of 64
 // states keep their prefix sums in LDS (-1 the default and the most, 1 024; 0
@@ -1330,6 +1347,51 @@ int hmc_write_posterior_draws(hmc_ctx *h, const char *path, int draws, uint64_t 
             if (c.pan.types[l] == 'S') fputc((char)row[l], fp);
             else fprintf(fp, "%d", row[l]);
           }
+        }
+        fputc('\n', fp);
+      }
+    }
+  }
+  const bool bad = ferror(fp) != 0;
+  if (fclose(fp) != 0 || bad) return c.fail(HMC_EIO, "Can not write file %s!", path);
+  return HMC_OK;
+}
+
+int hmc_write_map_phase(hmc_ctx *h, const char *path) {
+  if (!h || !path || !h->c.have_panel) return HMC_EARG;
+  Ctx &c = h->c;
+  const int n = c.nloc(), L = c.pan.L;
+  // individuals in batches whose haplotypes take at most 256 MiB of host memory, as hmc_write_posterior_draws:
+  // an individual's result does not depend on the others of its call
+  const size_t per = (size_t)2 * L;
+  const int nb = (int)std::max<size_t>(1, std::min<size_t>((size_t)std::max(n, 1), ((size_t)64 << 20) / per));
+  std::vector<int32_t> hap((size_t)nb * per), status(nb), indiv(nb);
+  std::vector<double> prob(nb);
+  FILE *fp = nullptr;
+  hmc::FileData d;
+  for (int b0 = 0; b0 < n || !fp; b0 += nb) {
+    const int k = std::max(0, std::min(nb, n - b0));
+    for (int i = 0; i < k; ++i) indiv[i] = c.i0 + b0 + i;
+    int rc;
+    // (the first batch before the file is opened: a call that fails leaves no file behind)
+    if ((rc = c.map_phase(k, indiv.data(), hap.data(), prob.data(), status.data()))) {
+      if (fp) fclose(fp);
+      return rc;
+    }
+    if (!fp) {
+      if (!(fp = fopen(path, "w"))) return c.fail(HMC_EIO, "Can not open file %s!", path);
+      d = writer_meta(c);
+      fprintf(fp, "Id\tStatus\tPosterior\n");
+    }
+    for (int i = 0; i < k; ++i) {
+      fprintf(fp, "%s\t%d\t%.17g\n", d.ids[indiv[i]].c_str(), status[i], prob[i]);
+      for (int side = 0; side < 2; ++side) {
+        const int32_t *row = hap.data() + ((size_t)i * 2 + side) * L;
+        for (int l = 0; l < L; ++l) {  // as the genotype files spell alleles: characters ('S') or integers ('M')
+          if (l) fputc(' ', fp);
+          if (row[l] < 0) fputc('?', fp);  // (a missing input allele in a row of status 1 or 2)
+          else if (c.pan.types[l] == 'S') fputc((char)row[l], fp);
+          else fprintf(fp, "%d", row[l]);
         }
         fputc('\n', fp);
       }

@@ -809,7 +809,7 @@ struct Ctx {
   void site_list(SiteList &sl) const;
   int site_group(const ExactArgs &x, int k, int dev_cu);
   // what the exact group runs after exact_fb in place of the trie walk
-  enum XpMode { XP_OFF = 0, XP_GENOTYPE = 1, XP_SWITCH = 2, XP_PAIR = 3, XP_DRAW = 4, XP_LIK = 5, XP_DOSE = 6 };
+  enum XpMode { XP_OFF = 0, XP_GENOTYPE = 1, XP_SWITCH = 2, XP_PAIR = 3, XP_DRAW = 4, XP_LIK = 5, XP_DOSE = 6, XP_MAP = 7 };
   XpMode xp_mode = XP_OFF;
   // Extended range (hmc_set_posterior_range): the four posterior calls run
   // exact_fb's scaled pass (ExactArgs::extended) and divide by its own total,
@@ -932,6 +932,18 @@ struct Ctx {
   // of the last call, as sw_* above; dr_ms_draw: exact_posterior_draws and draws_to_symbols
   double dr_ms_struct = 0, dr_ms_fb = 0, dr_ms_draw = 0;
   int dr_groups = 0, dr_pruned = 0;
+  // MAP phasing (hmc_map_phase): the most probable haplotype pair per asked
+  // individual and its exact posterior; exact_map_phase per group (XP_MAP)
+  // after exact_fb's forward-only pass, whose x-store slots the sweep
+  // overwrites (two doubles per state and record either way, so the groups
+  // stay those of the store budgets; slots of its own would halve them).
+  // Rows are the caller's, batches and device buffers the draws' with one draw.
+  int map_phase(int64_t n, const int32_t *indiv, int32_t *hap, double *prob, int32_t *status);
+  int map_group(const ExactArgs &x, const int32_t *ids, int k, int dev_cu);
+  DrawCall mp;  // the running call (draws = 1)
+  // of the last call, as dr_* above; mp_ms_sweep: exact_map_phase and draws_to_symbols
+  double mp_ms_struct = 0, mp_ms_fb = 0, mp_ms_sweep = 0;
+  int mp_groups = 0, mp_pruned = 0;
   DevBuf<unsigned long long> d_site_off;
   DevBuf<int32_t> d_site_locus, d_site_status;
   DevBuf<double> d_site_post;

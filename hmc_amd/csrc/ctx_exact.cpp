@@ -200,7 +200,7 @@ int Ctx::exact_group(const int32_t *ids, int k, const std::function<int(std::vec
   x.head_al = d_head_al.p;
   x.acc_freq = d_xacc.p;
   x.acc_prefix = d_xacc.p + xacc_nc;
-  x.forward_only = (xp_mode == XP_DRAW && dr_forward_only) || xp_mode == XP_LIK;
+  x.forward_only = (xp_mode == XP_DRAW && dr_forward_only) || xp_mode == XP_LIK || xp_mode == XP_MAP;
   // extended range: the posterior calls when asked for, the likelihoods always, the exact M-step never
   x.extended = xp_mode == XP_LIK || (xp_mode != XP_OFF && xp_extended);
   if (x.extended) {
@@ -262,6 +262,7 @@ int Ctx::exact_group(const int32_t *ids, int k, const std::function<int(std::vec
   if (xp_mode == XP_PAIR) return pair_group(x, ids, fm, k, dev_cu);
   if (xp_mode == XP_DRAW) return draw_group(x, ids, k, dev_cu);
   if (xp_mode == XP_DOSE) return dosage_group(x, ids, fm, k, dev_cu);
+  if (xp_mode == XP_MAP) return map_group(x, ids, k, dev_cu);
   if (xp_mode == XP_LIK) {  // the scaled totals of the group's individuals: nothing runs after exact_fb
     std::vector<double> tot(n);
     std::vector<int32_t> ex(n);
@@ -690,6 +691,71 @@ int Ctx::draw_group(const ExactArgs &x, const int32_t *ids, int k, int dev_cu) {
   return HMC_OK;
 }
 
+int Ctx::map_group(const ExactArgs &x, const int32_t *ids, int k, int dev_cu) {
+  const int L = pan.L, A = pan.amax;
+  std::vector<int32_t> sel;  // the group's individuals that the caller asked for
+  for (int q = 0; q < k; ++q)
+    if (mp.row_off[ids[q] + 1] > mp.row_off[ids[q]]) sel.push_back(ids[q]);
+  if (sel.empty()) return HMC_OK;
+  const size_t per = (size_t)2 * L;  // haplotype entries of one individual
+  const size_t cap = std::max<size_t>(1, DRAW_OUT_BYTES / (8 + (mp.hap ? per * 5 : 0)));
+  hipError_t e;
+  std::vector<int32_t> symtab((size_t)L * A, -1);  // the panel's symbol table, [locus][allele index]
+  for (int l = 0; l < L; ++l)
+    for (size_t j = 0; j < pan.sym[l].size(); ++j) symtab[(size_t)l * A + j] = pan.sym[l][j].first;
+  if (mp.hap &&
+      ((e = d_dr_sym.ensure(symtab.size())) ||
+       (e = hipMemcpyAsync(d_dr_sym.p, symtab.data(), symtab.size() * 4, hipMemcpyHostToDevice, st)) || (e = sync_st())))
+    return hipfail(e, "exact_map_phase");
+  std::vector<int32_t> h_st, h_hap;
+  std::vector<double> h_prob;
+  for (size_t pos = 0; pos < sel.size(); pos += cap) {
+    const int nb = (int)std::min(cap, sel.size() - pos);
+    const int grid = std::max(1, std::min(nb, dev_cu * 8));
+    ExactArgs xb = x;
+    MapArgs s;
+    if ((e = d_dr_order.ensure(nb)) || (e = d_dr_status.ensure(nb)) || (e = d_dr_prob.ensure(nb)) ||
+        (mp.hap && (e = d_dr_al.ensure((size_t)nb * per))) || (mp.hap && (e = d_dr_hap.ensure((size_t)nb * per))) ||
+        (e = hipMemsetAsync(d_dr_status.p, 0, (size_t)nb * 4, st)) ||  // the kernel writes the non-zero ones
+        (mp.hap && (e = hipMemsetAsync(d_dr_al.p, 0xFF, (size_t)nb * per, st))))
+      return hipfail(e, "exact_map_phase");
+    int rc;
+    if ((rc = upload_order(d_dr_order, sel.data() + pos, nb))) return rc;
+    xb.order = d_dr_order.p;
+    xb.n_order = nb;
+    s.al = mp.hap ? d_dr_al.p : nullptr;
+    s.prob = d_dr_prob.p;
+    s.status = d_dr_status.p;
+    hipEventRecord(ev[0], st);
+    if ((e = launch_exact_map_phase(xb, s, grid, st))) return hipfail(e, "exact_map_phase");
+    if (mp.hap && (e = launch_draws_to_symbols(d_dr_al.p, d_dr_sym.p, d_dr_hap.p, nb, L, 1, A, st)))
+      return hipfail(e, "draws_to_symbols");
+    hipEventRecord(ev[1], st);
+    h_st.resize(nb);
+    h_prob.resize(nb);
+    h_hap.resize(mp.hap ? (size_t)nb * per : 0);
+    if ((e = hipMemcpyAsync(h_st.data(), d_dr_status.p, (size_t)nb * 4, hipMemcpyDeviceToHost, st)) ||
+        (e = hipMemcpyAsync(h_prob.data(), d_dr_prob.p, (size_t)nb * 8, hipMemcpyDeviceToHost, st)) ||
+        (mp.hap && (e = hipMemcpyAsync(h_hap.data(), d_dr_hap.p, (size_t)nb * per * 4, hipMemcpyDeviceToHost, st))) ||
+        (e = sync_st()))
+      return hipfail(e, "exact_map_phase");
+    float ms = 0;
+    hipEventElapsedTime(&ms, ev[0], ev[1]);
+    xp_ms_sites += ms;
+    for (int u = 0; u < nb; ++u) {
+      const int bi = sel[pos + u];
+      mp.status[bi] = h_st[u];
+      if (h_st[u] != 0) continue;  // (the caller's rows get the input genotype)
+      for (int64_t w = mp.row_off[bi]; w < mp.row_off[bi + 1]; ++w) {
+        const int64_t row = mp.rows[w];
+        if (mp.prob) mp.prob[row] = h_prob[u];
+        if (mp.hap) std::copy(h_hap.begin() + (size_t)u * per, h_hap.begin() + (size_t)(u + 1) * per, mp.hap + (size_t)row * per);
+      }
+    }
+  }
+  return HMC_OK;
+}
+
 int Ctx::dosage_group(const ExactArgs &x, const int32_t *ids, const std::vector<int32_t> &fm, int k, int dev_cu) {
   const int NS = ds_ns_run, P = ds.P;
   std::vector<int32_t> sel;  // the group's individuals that the caller asked for
@@ -911,6 +977,69 @@ int Ctx::posterior_draws(int64_t n, const int32_t *indiv, int draws, uint64_t se
         for (int side = 0; side < 2; ++side)
           for (int l = 0; l < L; ++l)
             hap[(((size_t)q * draws + d) * 2 + side) * L + l] = pan.symbol(l, pan.idx[((size_t)(i0 + i) * 2 + side) * L + l]);
+  }
+  return HMC_OK;
+}
+
+int Ctx::map_phase(int64_t n, const int32_t *indiv, int32_t *hap, double *prob, int32_t *status) {
+  if (!have_estep) return fail(HMC_EARG, "MAP phasing needs an E-step first (hmc_resolve_all)");
+  if (estep_gen != model_gen)
+    return fail(HMC_EARG, "MAP phasing: the model changed since the last E-step (hmc_resolve_all again)");
+  if (pan.amax > 44) return fail(HMC_EUNSUPPORTED, "MAP phasing with more than 44 alleles per locus");
+  const int nl = nloc(), L = pan.L;
+  if (!indiv) n = nl;
+  if (n < 0) return fail(HMC_EARG, "MAP phasing: n = %lld is negative", (long long)n);
+  for (int64_t q = 0; indiv && q < n; ++q)
+    if (indiv[q] < i0 || indiv[q] >= i1)
+      return fail(HMC_EARG, "MAP phasing: entry %lld: individual %d is outside this rank's shard [%d, %d)", (long long)q,
+                  indiv[q], i0, i1);
+  mp_ms_struct = mp_ms_fb = mp_ms_sweep = 0;
+  mp_groups = mp_pruned = 0;
+  if (n == 0) return HMC_OK;
+  auto local = [&](int64_t q) { return indiv ? indiv[q] - i0 : (int)q; };
+  mp.draws = 1;
+  mp.hap = hap;
+  mp.prob = prob;
+  mp.row_off.assign((size_t)nl + 1, 0);
+  for (int64_t q = 0; q < n; ++q) ++mp.row_off[local(q) + 1];
+  for (int i = 0; i < nl; ++i) mp.row_off[i + 1] += mp.row_off[i];
+  mp.rows.assign((size_t)n, 0);
+  {
+    std::vector<int64_t> at(mp.row_off.begin(), mp.row_off.end() - 1);
+    for (int64_t q = 0; q < n; ++q) mp.rows[at[local(q)]++] = q;
+  }
+  mp.status.assign(nl, 1);
+  hipError_t er;
+  if ((er = d_xstatus.ensure(nl)) || (er = d_xre.ensure(nl)) || (er = d_xfmax.ensure(nl))) return hipfail(er, "MAP phasing");
+  // the pass counts in the genotype posteriors' fields: theirs are put back
+  const double g_struct = xp_ms_struct, g_fb = xp_ms_fb, g_sites = xp_ms_sites;
+  const int g_groups = xp_groups, g_pruned = xp_pruned;
+  std::vector<char> asked(nl, 0);  // the passes run over the individuals asked for, not the whole shard
+  for (int i = 0; i < nl; ++i) asked[i] = mp.row_off[i + 1] > mp.row_off[i];
+  const int rc = xp_pass(XP_MAP, "MAP phasing", &asked);
+  mp_ms_struct = xp_ms_struct;
+  mp_ms_fb = xp_ms_fb;
+  mp_ms_sweep = xp_ms_sites;
+  mp_groups = xp_groups;
+  mp_pruned = xp_pruned;
+  xp_ms_struct = g_struct;
+  xp_ms_fb = g_fb;
+  xp_ms_sites = g_sites;
+  xp_groups = g_groups;
+  xp_pruned = g_pruned;
+  mp.hap = nullptr;
+  mp.prob = nullptr;
+  if (rc) return rc;
+  for (int64_t q = 0; q < n; ++q) {
+    const int i = local(q), stt = mp.status[i];
+    if (status) status[q] = stt;
+    if (stt == 0) continue;
+    // unresolved, or P(genotype) subnormal: the input genotype, as hmc_get_resolutions gives it, at probability 0
+    if (prob) prob[q] = 0.0;
+    if (hap)
+      for (int side = 0; side < 2; ++side)
+        for (int l = 0; l < L; ++l)
+          hap[((size_t)q * 2 + side) * L + l] = pan.symbol(l, pan.idx[((size_t)(i0 + i) * 2 + side) * L + l]);
   }
   return HMC_OK;
 }

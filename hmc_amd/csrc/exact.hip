@@ -2025,4 +2025,285 @@ hipError_t launch_draws_to_symbols(const uint8_t *al, const int32_t *sym, int32_
   return hipGetLastError();
 }
 
+// MAP phasing (hmc_map_phase): the haplotype pair of largest exact posterior
+// and that posterior, by a max-product sweep over the records exact_fb sweeps
+// with sums, and a traceback in the same launch.
+// A pair's value is the product of its path's tpv, doubled if its two
+// haplotypes differ anywhere (the draws' prob rule): a pair behind a
+// homozygous prefix is two mirror paths of half each, and one state is reached
+// by all-homozygous prefixes and by heterozygous ones (variable-order contexts
+// forget history), so a state carries two values:
+//   Vh[t]  the best product over paths to t whose haplotypes are equal so far,
+//   Vd[t]  the best pair value (the 2 inside) over paths that differ already.
+// Head record: homozygous state (Vh, Vd) = (tpv, 0), heterozygous (0, 2 tpv).
+// Record j above it, state t with alleles (xa, xb), contributions r in record
+// order, primes for record j - 1:
+//   xa == xb   Vh = tpv max_r Vh'[pred r]    Vd = tpv max_r Vd'[pred r]
+//   else       Vh = 0                        Vd = tpv max_r max(Vd'[pred r], 2 Vh'[pred r])
+// One multiplication per state and label, after the maximum, so a power of two
+// on a whole record changes no choice.  Vh sits where exact_fb keeps fwd, Vd
+// where it keeps bwd: exact_fb has run forward-only over the group before (it
+// lays out x_off, flags the underflow that sends an individual through the
+// pruned records, and in extended range leaves the divisor xtot 2^-xtot_exp),
+// and this sweep overwrites its slots.  EXT: every record's 2 F values are
+// rescaled by the maximum over both labels (rescale_record; an entry more than
+// 2^1021 below the maximum loses bits — a path that far behind), the
+// cumulative exponent in the record's first spare word.  Regular range: raw
+// doubles; a best path is far less probable than the genotype, so on a long
+// panel its product leaves the doubles where P(genotype) is still normal — an
+// individual whose raw sweep meets a value below DBL_MIN is swept again at
+// once with rescaled records (the same choices wherever the raw values kept
+// their bits, by the line above), instead of being given up.  For the same
+// reason the traced product is kept as mantissa and power-of-two count in
+// both ranges: the same bits as the raw product wherever that stays normal.
+// No back-pointers: wave 0 re-derives each choice from the stored values.
+//   Final record: candidates (t, label) with index 2 t + label (h = 0, d = 1);
+//   the largest value, among equals the lowest index — a rule, so that neither
+//   the block size nor the reduction order enters.
+//   Going down from state t with label l: the contributions in record order,
+//   the first that attains the maximum of the sweep; l = h reads Vh', l = d at
+//   xa == xb reads Vd', l = d at xa != xb reads per contribution Vd' and then
+//   2 Vh' (taking the latter switches the label to h).  The lanes of wave 0
+//   take the candidates 64 at a time under the same (value, lowest index) rule.
+// Haplotypes and prob exactly as exact_posterior_draws spells and multiplies
+// them, in DrawArgs' byte layout with one draw per individual.
+__device__ inline void wave_best(double &v, unsigned &k) {  // the largest v, then the lowest k, in every lane
+#pragma unroll
+  for (int o = WAVE / 2; o > 0; o >>= 1) {
+    const double ov = __shfl_xor(v, o);
+    const unsigned ok = __shfl_xor(k, o);
+    if (ov > v || (ov == v && ok < k)) {
+      v = ov;
+      k = ok;
+    }
+  }
+}
+
+// The sweep of one individual (every thread of the block).  SCALE: every
+// record's 2 F values rescaled by the maximum over both labels, the cumulative
+// exponent in the record's first spare word.  Otherwise raw doubles, and *flag
+// is raised when a value that should be positive comes out below DBL_MIN: it
+// has lost bits or all of them, and a comparison above it could go wrong.
+// Ends on a barrier.
+template <bool SCALE>
+__device__ inline void map_sweep(const ExactArgs &a, const unsigned long long *roff, const unsigned long long *xo, int *flag) {
+  const int tid = threadIdx.x, NT = blockDim.x;
+  const int L = a.L, hl = a.head_len;
+  int ex = 0, Fp = 0;  // SCALE: the cumulative exponent (block-uniform); the states of the record below
+  {
+    const RecView R(a.rec + roff[hl], true);
+    double *vh = (double *)(a.x + xo[hl]), *vd = vh + R.F;
+    double m = 0.0;
+    for (int t = tid; t < R.F; t += NT) {
+      const bool homo = (R.hdr[t] >> 24) & 1u;
+      const double tpv = R.tpv[t];
+      vh[t] = homo ? tpv : 0.0;
+      vd[t] = homo ? 0.0 : tpv * 2.0;
+      if constexpr (SCALE) m = fmax(m, homo ? tpv : tpv * 2.0);
+    }
+    if constexpr (SCALE) {
+      ex += rescale_record(vh, 2 * R.F, m);
+      if (tid == 0) ((int32_t *)(vh + 2 * (size_t)R.F))[0] = ex;
+    } else {
+      __syncthreads();
+    }
+    Fp = R.F;
+  }
+  for (int j = hl + 1; j <= L; ++j) {
+    const RecView R(a.rec + roff[j], false);
+    const double *ph = (const double *)(a.x + xo[j - 1]), *pd = ph + Fp;
+    double *vh = (double *)(a.x + xo[j]), *vd = vh + R.F;
+    double m = 0.0;
+    for (int t = tid; t < R.F; t += NT) {
+      const uint32_t hd = R.hdr[t];
+      const bool homo = (hd & 0xFFu) == ((hd >> 8) & 0xFFu);
+      double mh = 0.0, md = 0.0;
+      for (uint32_t r = R.cb[t]; r < R.cb[t + 1]; ++r) {
+        const uint32_t p = cw_state(R.ct[r]);
+        const double h = ph[p], d = pd[p];
+        if (homo) {
+          mh = fmax(mh, h);
+          md = fmax(md, d);
+        } else {
+          md = fmax(md, fmax(d, 2.0 * h));
+        }
+      }
+      const double tpv = R.tpv[t];
+      const double h = homo ? tpv * mh : 0.0, d = tpv * md;
+      vh[t] = h;
+      vd[t] = d;
+      if constexpr (SCALE) m = fmax(m, fmax(h, d));
+      else if ((mh > 0.0 && homo && h < SITE_PG_MIN) || (md > 0.0 && d < SITE_PG_MIN)) *flag = 1;
+    }
+    if constexpr (SCALE) {
+      ex += rescale_record(vh, 2 * R.F, m);
+      if (tid == 0) ((int32_t *)(vh + 2 * (size_t)R.F))[0] = ex;
+    } else {
+      __syncthreads();
+    }
+    Fp = R.F;
+  }
+}
+
+template <bool EXT>
+__global__ __launch_bounds__(256) void exact_map_phase(ExactArgs a, MapArgs s) {
+  __shared__ double bv[4];
+  __shared__ unsigned bk[4];
+  __shared__ int flag;
+  const int tid = threadIdx.x, NT = blockDim.x, lane = tid & (WAVE - 1), wave = tid / WAVE, nw = NT / WAVE;
+  const int L = a.L, hl = a.head_len;
+  for (int q = blockIdx.x; q < a.n_order; q += gridDim.x) {  // block-uniform
+    const int bi = a.order[q];
+    const int st0 = a.status[bi];
+    const double pg = EXT ? a.xtot[bi] : a.gprob[bi];
+    const int pge = EXT ? -a.xtot_exp[bi] : 0;  // P(genotype) = pg 2^pge
+    const bool resolved = (st0 == EST_OK || st0 == EST_OK_PRUNED) && pg > 0.0 && !isinf(pg);
+    if (!resolved || (!EXT && pg < SITE_PG_MIN)) {  // the host writes the input genotype: unresolved (1), P(genotype) subnormal (2)
+      if (tid == 0) s.status[q] = resolved ? 2 : 1;
+      continue;
+    }
+    const unsigned long long *roff = a.rec_off + (size_t)bi * (L + 1);
+    const unsigned long long *xo = a.x_off + (size_t)bi * (L + 1);
+    // the sweep: raw doubles in the regular range, and again with rescaled records if those underflow
+    if constexpr (EXT) {
+      map_sweep<true>(a, roff, xo, &flag);
+    } else {
+      if (tid == 0) flag = 0;  // (every thread has read the previous individual's flag before the barrier of its final reduction)
+      __syncthreads();
+      map_sweep<false>(a, roff, xo, &flag);
+      if (flag != 0) map_sweep<true>(a, roff, xo, &flag);  // block-uniform: read behind the sweep's last barrier
+    }
+    // the final record's best candidate
+    const RecView RL(a.rec + roff[L], L == hl);
+    const double *vL = (const double *)(a.x + xo[L]);
+    double best = -1.0;
+    unsigned bkey = 0xFFFFFFFFu;
+    for (int t = tid; t < RL.F; t += NT) {  // ascending: strictly larger only
+      const double h = vL[t], d = vL[RL.F + t];
+      if (h > best) {
+        best = h;
+        bkey = 2u * (unsigned)t;
+      }
+      if (d > best) {
+        best = d;
+        bkey = 2u * (unsigned)t + 1u;
+      }
+    }
+    wave_best(best, bkey);
+    if (lane == 0) {
+      bv[wave] = best;
+      bk[wave] = bkey;
+    }
+    __syncthreads();
+    if (wave != 0) continue;  // (wave 0 passes the next individual's barriers after its traceback)
+    best = bv[0];
+    bkey = bk[0];
+    for (int w = 1; w < nw; ++w)
+      if (bv[w] > best || (bv[w] == best && bk[w] < bkey)) {
+        best = bv[w];
+        bkey = bk[w];
+      }
+    if (!(best > 0.0)) {  // (no path with a positive product: the host writes the input genotype)
+      if (lane == 0) s.status[q] = 1;
+      continue;
+    }
+    auto put = [&](int k, int side, uint32_t x) {
+      if (s.al && lane == 0) s.al[((size_t)q * 2 + side) * L + k] = (uint8_t)x;
+    };
+    int t = (int)(bkey >> 1);
+    bool lab_d = bkey & 1u;
+    int par = 0;
+    bool het = false, dead = false;
+    double p = 1.0;
+    int pe = 0;  // the true product is p 2^pe (a raw product of a long panel's path underflows where its quotient does not)
+    auto renorm = [&]() {
+      int e;
+      p = frexp(p, &e);
+      pe += e;
+    };
+    for (int j = L; j > hl; --j) {  // wave-uniform
+      const RecView R(a.rec + roff[j], false);
+      const uint32_t hd = R.hdr[t], xa = hd & 0xFFu, xb = (hd >> 8) & 0xFFu;
+      const uint32_t r0 = R.cb[t], r1 = R.cb[t + 1];
+      const double tpv = R.tpv[t];
+      const int Fq = (int)a.rec[roff[j - 1]];
+      const double *ph = (const double *)(a.x + xo[j - 1]), *pd = ph + Fq;
+      put(j - 1, par, xa);
+      put(j - 1, par ^ 1, xb);
+      het |= xa != xb;
+      p = j == L ? tpv : p * tpv;
+      renorm();
+      const bool both = lab_d && xa != xb;
+      double cv = -1.0;
+      unsigned ck = 0xFFFFFFFFu, cw = 0u;
+      for (uint32_t rb = r0; rb < r1; rb += WAVE) {  // 64 contributions at a time; an earlier batch wins a tie
+        const uint32_t r = rb + (uint32_t)lane;
+        double v = -1.0;
+        unsigned k = 0xFFFFFFFFu;
+        uint32_t w = 0u;
+        if (r < r1) {
+          w = R.ct[r];
+          const uint32_t ps = cw_state(w);
+          k = 2u * (unsigned)lane;
+          if (both) {
+            const double d = pd[ps], h2 = 2.0 * ph[ps];
+            v = d;
+            if (h2 > d) {
+              v = h2;
+              k += 1u;
+            }
+          } else {
+            v = lab_d ? pd[ps] : ph[ps];
+          }
+        }
+        wave_best(v, k);
+        if (v > cv) {
+          cv = v;
+          ck = k;
+          cw = __shfl(w, (int)(k >> 1));
+        }
+      }
+      if (!(cv > 0.0)) {  // (a state no path reaches is never chosen; if one were, the individual counts as unresolved)
+        dead = true;
+        break;
+      }
+      if (ck & 1u) lab_d = false;
+      if (cw_rev(cw)) par ^= 1;
+      t = (int)cw_state(cw);
+    }
+    if (!dead) {  // the head state: loci below head_len
+      const RecView H(a.rec + roff[hl], true);
+      const double tpv = H.tpv[t];
+      p = L == hl ? tpv : p * tpv;
+      renorm();
+      if (hl == 1) {
+        const uint32_t hd = H.hdr[t], xa = hd & 0xFFu, xb = (hd >> 8) & 0xFFu;
+        put(0, par, xa);
+        put(0, par ^ 1, xb);
+        het |= xa != xb;
+      } else {
+        const uint32_t *plo = H.cb + H.F + 1, *phi = plo + H.F;
+        const uint8_t *pa = a.head_al + (size_t)plo[t] * hl, *pb = a.head_al + (size_t)phi[t] * hl;
+        for (int k = 0; k < hl; ++k) {
+          put(k, par, pa[k]);
+          put(k, par ^ 1, pb[k]);
+          het |= pa[k] != pb[k];
+        }
+      }
+    }
+    if (lane == 0) {
+      if (dead) s.status[q] = 1;
+      if (s.prob) s.prob[q] = dead ? 0.0 : ldexp((het ? p * 2.0 : p) / pg, pe - pge);
+    }
+  }
+}
+
+hipError_t launch_exact_map_phase(const ExactArgs &a, const MapArgs &s, int grid, hipStream_t st, int block) {
+  if (a.n_order <= 0) return hipSuccess;
+  if (grid < 1 || !s.status || block < WAVE || block > 256 || block % WAVE) return hipErrorInvalidValue;
+  if (a.extended) hipLaunchKernelGGL(exact_map_phase<true>, dim3(grid), dim3(block), 0, st, a, s);
+  else hipLaunchKernelGGL(exact_map_phase<false>, dim3(grid), dim3(block), 0, st, a, s);
+  return hipGetLastError();
+}
+
 }  // namespace hmc

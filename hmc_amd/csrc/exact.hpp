@@ -225,4 +225,21 @@ hipError_t launch_exact_posterior_draws(const ExactArgs &a, const DrawArgs &s, i
 hipError_t launch_draws_to_symbols(const uint8_t *al, const int32_t *sym, int32_t *hap, int slots, int L, int D, int W,
                                    hipStream_t st);
 
+// MAP phasing (exact_map_phase): the most probable haplotype pair of every
+// individual of the group and its exact posterior, by a max-product sweep
+// over the records and a traceback in the same launch.  The sweep keeps two
+// doubles per state and record, in the x-store slots exact_fb's forward-only
+// pass over the same group has laid out (x_off) and filled: Vh over fwd[F], Vd
+// over bwd[F] — after this launch the store holds no forward values.
+// Individual q of the group (ExactArgs::order) owns output slot q; al in
+// DrawArgs' layout with one draw, al[slot][side][locus] bytes (may be NULL);
+// status is zeroed by the caller: the kernel writes the non-zero ones only.
+struct MapArgs {
+  uint8_t *al = nullptr;           // [slots][2][L] allele indices
+  double *prob = nullptr;          // [slots]
+  int32_t *status = nullptr;       // [slots] 0 ok, 1 unresolved, 2 P(genotype) subnormal
+};
+// after exact_fb (forward only will do) over the same group; block sizes 64 .. 256 and the grid do not change the bits
+hipError_t launch_exact_map_phase(const ExactArgs &a, const MapArgs &s, int grid, hipStream_t st, int block = 256);
+
 }  // namespace hmc

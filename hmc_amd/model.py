@@ -704,6 +704,35 @@ class HaploModel:
         self._check(lib().hmc_last_draw_stats(self._h, C.byref(s), C.byref(f), C.byref(k), C.byref(g), C.byref(p)))
         return dict(structure_ms=s.value, fb_ms=f.value, draw_ms=k.value, groups=g.value, n_pruned=p.value)
 
+    def map_phase(self, indiv=None) -> dict:
+        """The most probable haplotype pair under the model of the last
+        resolve_all and its exact posterior (hmc_map_phase): for the panel
+        indices `indiv` (any order, repeats allowed; None = this rank's whole
+        shard) hap[n, 2, L] symbols, prob[n], status[n] (0 ok; 1 individual
+        unresolved, 2 its P(genotype) subnormal: the input genotype, prob 0).
+        An exact max-product sweep over the whole lattice: resolutions() is
+        the best pair of the E-step's k-best beam, which can miss it."""
+        if indiv is None:
+            qi, n = None, self.i1 - self.i0
+        else:
+            qi = np.ascontiguousarray(indiv, np.int32).reshape(-1)
+            n = len(qi)
+        out = dict(hap=np.zeros((n, 2, self.L), np.int32), prob=np.zeros(n, np.float64), status=np.zeros(n, np.int32))
+        self._check(lib().hmc_map_phase(self._h, n, None if qi is None else _p(qi, C.c_int32), _p(out["hap"], C.c_int32),
+                                        _p(out["prob"], C.c_double), _p(out["status"], C.c_int32)))
+        return out
+
+    def map_stats(self) -> dict:
+        """Device ms and counts of the last map_phase (hmc_last_map_stats)."""
+        s, f, k = C.c_double(), C.c_double(), C.c_double()
+        g, p = C.c_int(), C.c_int()
+        self._check(lib().hmc_last_map_stats(self._h, C.byref(s), C.byref(f), C.byref(k), C.byref(g), C.byref(p)))
+        return dict(structure_ms=s.value, fb_ms=f.value, sweep_ms=k.value, groups=g.value, n_pruned=p.value)
+
+    def write_map_phase(self, path: str):
+        """map_phase of the whole shard as text, three lines per individual (hmc_write_map_phase)."""
+        self._check(lib().hmc_write_map_phase(self._h, path.encode()))
+
     def set_posterior_range(self, extended: bool):
         """Range of genotype_posteriors, switch_posteriors, pair_posteriors,
         posterior_draws and their write_* forms (hmc_set_posterior_range).

@@ -246,7 +246,8 @@ int hmc_get_resolutions(hmc_ctx *ctx, int32_t *out);
  * P({x, y} at the locus | genotype) = the sum of forward x backward likelihood
  * over the lattice states that carry {x, y}, over P(genotype) — exact, with no
  * k-best cut and no sampling (hmc_get_resolutions gives the alleles of the
- * single most probable pair only).  Needs a preceding hmc_resolve_all (any
+ * best pair of the E-step's k-best list only; hmc_map_phase gives the most
+ * probable pair).  Needs a preceding hmc_resolve_all (any
  * E-step mode); runs its own forward-backward pass and changes no later
  * result.  With indiv, locus, status and post all NULL the call only counts:
  * *n_sites from the panel, *n_pairs = A (A + 1) / 2 for A = max_alleles
@@ -490,8 +491,82 @@ int hmc_posterior_draws(hmc_ctx *ctx, int64_t n, const int32_t *indiv, int draws
  * kernel and of the draw kernel with its transposition; groups the individuals ran in;
  * individuals on pruned records.  Replaces no reference interface. */
 int hmc_last_draw_stats(const hmc_ctx *ctx, double *structure_ms, double *fb_ms, double *draw_ms, int *groups, int *n_pruned);
+/* MAP phasing: the haplotype pair of largest exact posterior P(pair |
+ * genotype) under the model of the last E-step, and that posterior — the
+ * phasing to report, with its confidence.  (hmc_get_resolutions gives the best
+ * pair of the E-step's k-best list, which is the most probable pair only when
+ * the maximiser survived the beam; a posterior draw finds the mode by luck.)
+ * indiv[n] are panel indices inside this rank's shard, in any order, repeats
+ * allowed; indiv = NULL means the whole shard (n is ignored).  Outputs, any of
+ * which may be NULL: hap[n][2][L] symbols, prob[n], status[n]; status 0 / 1 / 2
+ * as for hmc_posterior_draws, rows of status 1 and 2 carry the input genotype
+ * and prob 0.
+ *
+ * The lattice is the one stated under hmc_posterior_draws.  A pair's value is
+ * the draws' prob numerator: the product of its path's tpv, doubled if the two
+ * haplotypes differ anywhere.  A heterozygous pair behind a homozygous prefix
+ * is two mirror paths of half each, and one state is reached by homozygous and
+ * by heterozygous prefixes (variable-order contexts forget history), so the
+ * max-product sweep carries two values per state t of a record:
+ *   Vh[t]  the best product over paths to t whose two haplotypes are equal so far,
+ *   Vd[t]  the best pair value, the factor 2 inside, over paths that differ already.
+ *   Head record: a homozygous head state has (Vh, Vd) = (tpv, 0), a
+ *   heterozygous one (0, tpv * 2.0).
+ *   Record j above it, state t with alleles (xa, xb) and contributions r in
+ *   record order, primes for record j - 1:
+ *     xa == xb:  Vh[t] = tpv[t] * max_r Vh'[pred r],  Vd[t] = tpv[t] * max_r Vd'[pred r]
+ *     else:      Vh[t] = 0,  Vd[t] = tpv[t] * max_r max(Vd'[pred r], 2.0 * Vh'[pred r])
+ *   — one multiplication per state and label, after the maximum.
+ *   Tie rules.  Final record: candidates (t, label) in order of t, Vh before
+ *   Vd within a state; the largest value, among equals the first.  Going down
+ *   from state t with label l at record j: the first contribution in record
+ *   order that attains the maximum above; l = h reads Vh', l = d with xa == xb
+ *   reads Vd', l = d with xa != xb reads per contribution Vd' and then
+ *   2.0 * Vh' (choosing the latter continues with label h).
+ *   Haplotypes are spelled as a draw's: side parity, flipped by the chosen
+ *   contribution's rev flag after the state's alleles are written; the head
+ *   state supplies loci below head_len.  Which haplotype comes first carries
+ *   no information.
+ *   prob by the draws' rule, so that the two calls mean the same number: tpv
+ *   of the final state times tpv of each chosen state down to the head record,
+ *   one multiplication each in that order; doubled if the haplotypes differ at
+ *   any locus; divided by P(genotype).
+ * Range (hmc_set_posterior_range).  Regular: raw doubles, the divisor is the
+ * last E-step's P(genotype); an individual whose forward likelihood underflows
+ * goes through the pruned records as in the other posterior calls, and one
+ * whose max-product values fall below DBL_MIN (the best pair is far less
+ * probable than the genotype, so on long panels its product underflows where
+ * P(genotype) does not) is swept again with rescaled records as in extended
+ * range — the same choices wherever the raw values kept their bits — so
+ * status 0 / 1 / 2 fall exactly where hmc_posterior_draws puts them; the traced
+ * product is kept as mantissa and exponent in both ranges.  Extended:
+ * every record's values (both labels) are multiplied by the power of two that
+ * brings the record's largest into [0.5, 1) — exact, so no choice changes,
+ * except that an entry more than 2^1021 below its record's maximum loses bits,
+ * which could only matter for a path that far behind — the traced product is
+ * kept as mantissa and exponent, the divisor is the scaled forward pass's own
+ * total, and status 2 never occurs.
+ * The result's bits depend on the model, the range setting and the individual
+ * alone: not on the other individuals of the call, sharding, launch shapes,
+ * store budgets or groups.  An individual with a missing allele at a head
+ * locus gets its loci below head_len from the reference's head pairing, which
+ * is not a phasing model.
+ * Needs a preceding hmc_resolve_all (any E-step mode); runs its own exact-mode
+ * structure pass, forward pass (which lays out the value store, finds the
+ * underflowing individuals and, in extended range, gives the divisor) and
+ * max-product sweep with traceback, over the individuals asked for only, and
+ * changes no later result.  n = 0 is HMC_OK with no device work.  HMC_EARG and
+ * HMC_EUNSUPPORTED as for hmc_posterior_draws.
+ * Replaces no reference interface. */
+int hmc_map_phase(hmc_ctx *ctx, int64_t n, const int32_t *indiv, int32_t *hap, double *prob, int32_t *status);
+/* Last hmc_map_phase: device ms of its structure passes, of the forward
+ * kernel and of the max-product sweep with its traceback and transposition;
+ * groups the individuals ran in; individuals on pruned records.  Replaces no
+ * reference interface. */
+int hmc_last_map_stats(const hmc_ctx *ctx, double *structure_ms, double *fb_ms, double *sweep_ms, int *groups, int *n_pruned);
 /* Range of the posterior family (hmc_genotype_posteriors, hmc_switch_posteriors,
- * hmc_pair_posteriors, hmc_posterior_draws and their hmc_write_* forms).
+ * hmc_pair_posteriors, hmc_posterior_draws, hmc_map_phase and their
+ * hmc_write_* forms).
  * extended = 0 (default): the forward-backward pass keeps raw doubles and
  * divides by the last E-step's P(genotype); an individual whose P(genotype) is
  * below DBL_MIN gets status 2, one whose forward likelihood underflowed to 0
@@ -649,6 +724,15 @@ int hmc_write_pair_posteriors(hmc_ctx *ctx, const char *path, int span);
  * separated by single spaces.  Needs a preceding hmc_resolve_all or hmc_run;
  * HMC_EARG for draws < 1.  Replaces no reference interface. */
 int hmc_write_posterior_draws(hmc_ctx *ctx, const char *path, int draws, uint64_t seed);
+/* hmc_map_phase of the whole shard as text (hmc_resolve --output-map FILE):
+ * the header "Id\tStatus\tPosterior", then per individual of the shard, in
+ * order, three lines: the individual's id, its status and the pair's posterior
+ * as %.17g (reads back to the same double), tab-separated; then each of the
+ * two haplotypes on a line of its own, its alleles spelled as
+ * hmc_write_posterior_draws spells them and separated by single spaces ('?'
+ * for a missing input allele in a row of status 1 or 2).  Needs a preceding
+ * hmc_resolve_all or hmc_run.  Replaces no reference interface. */
+int hmc_write_map_phase(hmc_ctx *ctx, const char *path);
 /* hmc_haplotype_dosages of the whole shard as text (hmc_resolve
  * --output-dosages FILE --haplotypes HAPFILE): the header
  * "Id\tHaplotype\tDosage", then one line per individual of status 0 and per

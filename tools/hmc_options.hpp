@@ -24,7 +24,8 @@ struct Options {
   bool have_draws = false, have_seed = false;
   std::string output_dosages;          // --output-dosages FILE
   std::string haplotypes;              // --haplotypes HAPFILE (required with it)
-  bool extended_range = false;         // --extended-range (needs one of the --output-*posteriors / --output-draws / --output-dosages options)
+  std::string output_map;              // --output-map FILE
+  bool extended_range = false;         // --extended-range (needs one of the --output-*posteriors / --output-draws / --output-dosages / --output-map options)
 };
 
 // --output-posteriors (no reference counterpart): <first file>.posteriors, the
@@ -59,7 +60,9 @@ constexpr const char *USAGE =
     "  --output-dosages FILE --haplotypes HAPFILE  write FILE: for every individual the exact expected\n"
     "                        copies of each haplotype of HAPFILE (lines: name start a a a ... [| b b b ...],\n"
     "                        start the 0-based first locus, alleles as the genotype files spell them, ? = any)\n"
-    "  --extended-range      the five options above in extended range: individuals whose likelihood\n"
+    "  --output-map FILE     write FILE: for every individual the most probable haplotype pair under the\n"
+    "                        final model, found exactly (no k-best cut), with its status and posterior\n"
+    "  --extended-range      the six options above in extended range: individuals whose likelihood\n"
     "                        underflows a double (panels of more than about 1 200 loci) get lines too";
 
 // 0 on success; otherwise `err` says what is wrong (a missing value, an
@@ -94,6 +97,7 @@ inline int parse_options(int argc, const char *const *argv, Options &o, std::str
     else if (a == "--output-draws") { if (!next()) return 1; o.output_draws = v; }
     else if (a == "--draws") { if (!next()) return 1; o.draws = atoi(v); o.have_draws = true; }
     else if (a == "--output-dosages") { if (!next()) return 1; o.output_dosages = v; }
+    else if (a == "--output-map") { if (!next()) return 1; o.output_map = v; }
     else if (a == "--haplotypes") { if (!next()) return 1; o.haplotypes = v; }
     else if (a == "--extended-range") o.extended_range = true;
     else if (a == "--seed") { if (!next()) return 1; o.seed = strtoull(v, nullptr, 10); o.have_seed = true; }
@@ -128,8 +132,8 @@ inline int parse_options(int argc, const char *const *argv, Options &o, std::str
     return 1;
   }
   if (o.extended_range && !o.output_posteriors && !o.output_switch_posteriors && o.output_pair_posteriors.empty() &&
-      o.output_draws.empty() && o.output_dosages.empty()) {
-    err = "--extended-range needs --output-posteriors, --output-switch-posteriors, --output-pair-posteriors, --output-draws or --output-dosages\n" +
+      o.output_draws.empty() && o.output_dosages.empty() && o.output_map.empty()) {
+    err = "--extended-range needs --output-posteriors, --output-switch-posteriors, --output-pair-posteriors, --output-draws, --output-dosages or --output-map\n" +
           std::string(USAGE);
     return 1;
   }

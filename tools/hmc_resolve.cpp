@@ -13,7 +13,8 @@
 //               [--output-patterns x] [--output-posteriors] [--output-switch-posteriors]
 //               [--output-pair-posteriors FILE --pair-span K]
 //               [--output-draws FILE [--draws 100] [--seed 0]]
-//               [--output-dosages FILE --haplotypes HAPFILE] [--extended-range] [--device 0] datafile ...
+//               [--output-dosages FILE --haplotypes HAPFILE] [--output-map FILE] [--extended-range]
+//               [--device 0] datafile ...
 // --output-posteriors (no reference counterpart) writes <first file>.posteriors:
 // genotype posteriors at the loci with a missing input allele, under the final
 // model (hmc_write_posteriors).  --output-switch-posteriors (none either)
@@ -28,7 +29,10 @@
 // --output-dosages FILE --haplotypes HAPFILE (none either) writes FILE: for
 // every individual the exact expected copies of each haplotype listed in
 // HAPFILE (hmc_hapfile.hpp; hmc_write_haplotype_dosages).
-// --extended-range (none either) runs those five in extended range
+// --output-map FILE (none either) writes FILE: every individual's most
+// probable haplotype pair under the final model, found exactly, with its
+// status and posterior (hmc_write_map_phase).
+// --extended-range (none either) runs those six in extended range
 // (hmc_set_posterior_range): individuals whose likelihood underflows a double
 // get lines too.
 #include <cstdio>
@@ -139,6 +143,9 @@ int main(int argc, char **argv) {
     if ((rc = hmc_write_haplotype_dosages(ctx, o.output_dosages.c_str(), (int)hn.size(), hn.data(), haps.start.data(),
                                           haps.len.data(), haps.maxlen, ha.data(), haps.two_sided ? hb.data() : nullptr)))
       die("hmc_write_haplotype_dosages");
+  }
+  if (!o.output_map.empty()) {  // of the same E-step
+    if ((rc = hmc_write_map_phase(ctx, o.output_map.c_str()))) die("hmc_write_map_phase");
   }
   hmc_ctx_destroy(ctx);
   return 0;
