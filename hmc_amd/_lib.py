@@ -101,6 +101,11 @@ _SIGS = [
     ("hmc_map_phase", _i, [_vp, C.c_int64, _P(C.c_int32), _P(C.c_int32), _P(_d), _P(C.c_int32)]),
     ("hmc_last_map_stats", _i, [_vp, _P(_d), _P(_d), _P(_d), _P(_i), _P(_i)]),
     ("hmc_write_map_phase", _i, [_vp, _cp]),
+    ("hmc_ranked_phasings", _i, [_vp, C.c_int64, _P(C.c_int32), _i, _P(C.c_int32), _P(_d), _P(C.c_int32), _P(C.c_int32)]),
+    ("hmc_last_ranked_stats", _i, [_vp, _P(_d), _P(_d), _P(_d), _P(_i), _P(_i), _P(_i)]),
+    ("hmc_set_ranked_tuning", _i, [_vp, _u64]),
+    ("hmc_last_ranked_batches", _i, [_vp, _P(_i)]),
+    ("hmc_write_ranked_phasings", _i, [_vp, _cp, _i]),
     ("hmc_set_posterior_range", _i, [_vp, _i]),
     ("hmc_genotype_likelihoods", _i, [_vp, C.c_int64, _P(C.c_int32), _P(_d), _P(C.c_int32), _P(C.c_int32)]),
     ("hmc_last_likelihood_stats", _i, [_vp, _P(_d), _P(_d), _P(_i)]),

@@ -1079,6 +1079,42 @@ int hmc_last_map_stats(const hmc_ctx *h, double *structure_ms, double *fb_ms, do
   return HMC_OK;
 }
 
+int hmc_ranked_phasings(hmc_ctx *h, int64_t n, const int32_t *indiv, int k, int32_t *hap, double *prob, int32_t *count,
+                        int32_t *status) {
+  if (!h) return HMC_EARG;
+  Ctx &c = h->c;
+  if (!c.have_panel) return c.fail(HMC_EARG, "no panel loaded");
+  return c.ranked_phasings(n, indiv, k, hap, prob, count, status);
+}
+
+int hmc_last_ranked_stats(const hmc_ctx *h, double *structure_ms, double *fb_ms, double *sweep_ms, int *groups, int *n_pruned,
+                          int *k_built) {
+  if (!h) return HMC_EARG;
+  if (structure_ms) *structure_ms = h->c.rk_ms_struct;
+  if (fb_ms) *fb_ms = h->c.rk_ms_fb;
+  if (sweep_ms) *sweep_ms = h->c.rk_ms_sweep;
+  if (groups) *groups = h->c.rk_groups;
+  if (n_pruned) *n_pruned = h->c.rk_pruned;
+  if (k_built) *k_built = h->c.rk_built;
+  return HMC_OK;
+}
+
+// Test seam of hmc_ranked_phasings (not in the public header; results do not
+// depend on it): store_bytes = the budget of the list store, which decides how
+// many individuals of a group go through one launch (0: the value store's
+// budget).  hmc_last_ranked_batches: the launches of the last call.
+int hmc_set_ranked_tuning(hmc_ctx *h, uint64_t store_bytes) {
+  if (!h) return HMC_EARG;
+  h->c.rk_store_bytes = store_bytes;
+  return HMC_OK;
+}
+
+int hmc_last_ranked_batches(const hmc_ctx *h, int *batches) {
+  if (!h) return HMC_EARG;
+  if (batches) *batches = h->c.rk_batches;
+  return HMC_OK;
+}
+
 // Test seam of hmc_posterior_draws (not in the public header; results do not
 // depend on it): lds_chunks = final records of at most this many chunks of 64
 // states keep their prefix sums in LDS (-1 the default and the most, 1 024; 0
@@ -1392,6 +1428,54 @@ int hmc_write_map_phase(hmc_ctx *h, const char *path) {
           if (row[l] < 0) fputc('?', fp);  // (a missing input allele in a row of status 1 or 2)
           else if (c.pan.types[l] == 'S') fputc((char)row[l], fp);
           else fprintf(fp, "%d", row[l]);
+        }
+        fputc('\n', fp);
+      }
+    }
+  }
+  const bool bad = ferror(fp) != 0;
+  if (fclose(fp) != 0 || bad) return c.fail(HMC_EIO, "Can not write file %s!", path);
+  return HMC_OK;
+}
+
+int hmc_write_ranked_phasings(hmc_ctx *h, const char *path, int k) {
+  if (!h || !path || !h->c.have_panel) return HMC_EARG;
+  Ctx &c = h->c;
+  if (k < 1 || k > hmc::RANK_K_MAX) return c.fail(HMC_EARG, "ranked phasings: k = %d is outside [1, %d]", k, hmc::RANK_K_MAX);
+  const int n = c.nloc(), L = c.pan.L;
+  // individuals in batches whose haplotypes take at most 256 MiB of host memory, as hmc_write_posterior_draws:
+  // an individual's result does not depend on the others of its call
+  const size_t per = (size_t)2 * L * k;
+  const int nb = (int)std::max<size_t>(1, std::min<size_t>((size_t)std::max(n, 1), ((size_t)64 << 20) / per));
+  std::vector<int32_t> hap((size_t)nb * per), status(nb), count(nb), indiv(nb);
+  std::vector<double> prob((size_t)nb * k);
+  FILE *fp = nullptr;
+  hmc::FileData d;
+  for (int b0 = 0; b0 < n || !fp; b0 += nb) {
+    const int m = std::max(0, std::min(nb, n - b0));
+    for (int i = 0; i < m; ++i) indiv[i] = c.i0 + b0 + i;
+    int rc;
+    // (the first batch before the file is opened: a call that fails leaves no file behind)
+    if ((rc = c.ranked_phasings(m, indiv.data(), k, hap.data(), prob.data(), count.data(), status.data()))) {
+      if (fp) fclose(fp);
+      return rc;
+    }
+    if (!fp) {
+      if (!(fp = fopen(path, "w"))) return c.fail(HMC_EIO, "Can not open file %s!", path);
+      d = writer_meta(c);
+      fprintf(fp, "Id\tRank\tPosterior\tHaplotype0\tHaplotype1\n");
+    }
+    for (int i = 0; i < m; ++i) {
+      if (status[i] != 0) continue;
+      for (int r = 0; r < count[i]; ++r) {
+        fprintf(fp, "%s\t%d\t%.17g", d.ids[indiv[i]].c_str(), r, prob[(size_t)i * k + r]);
+        for (int side = 0; side < 2; ++side) {
+          const int32_t *row = hap.data() + (((size_t)i * k + r) * 2 + side) * L;
+          for (int l = 0; l < L; ++l) {  // as the genotype files spell alleles: characters ('S') or integers ('M')
+            fputc(l ? ' ' : '\t', fp);
+            if (c.pan.types[l] == 'S') fputc((char)row[l], fp);
+            else fprintf(fp, "%d", row[l]);
+          }
         }
         fputc('\n', fp);
       }

@@ -809,7 +809,7 @@ struct Ctx {
   void site_list(SiteList &sl) const;
   int site_group(const ExactArgs &x, int k, int dev_cu);
   // what the exact group runs after exact_fb in place of the trie walk
-  enum XpMode { XP_OFF = 0, XP_GENOTYPE = 1, XP_SWITCH = 2, XP_PAIR = 3, XP_DRAW = 4, XP_LIK = 5, XP_DOSE = 6, XP_MAP = 7 };
+  enum XpMode { XP_OFF = 0, XP_GENOTYPE = 1, XP_SWITCH = 2, XP_PAIR = 3, XP_DRAW = 4, XP_LIK = 5, XP_DOSE = 6, XP_MAP = 7, XP_RANK = 8 };
   XpMode xp_mode = XP_OFF;
   // Extended range (hmc_set_posterior_range): the four posterior calls run
   // exact_fb's scaled pass (ExactArgs::extended) and divide by its own total,
@@ -944,6 +944,28 @@ struct Ctx {
   // of the last call, as dr_* above; mp_ms_sweep: exact_map_phase and draws_to_symbols
   double mp_ms_struct = 0, mp_ms_fb = 0, mp_ms_sweep = 0;
   int mp_groups = 0, mp_pruned = 0;
+  // Ranked phasings (hmc_ranked_phasings): the k most probable haplotype
+  // pairs per asked individual, each once, with their exact posteriors;
+  // exact_ranked_phasings per group (XP_RANK) after exact_fb's forward-only
+  // pass.  The lists (24 KL bytes per state and record) have a device store of
+  // their own, d_rk_store, and the group's individuals go through in batches
+  // whose lists fit its budget: rank_budget_bytes(), the bytes of the value
+  // store's budget (trace_budget words) unless hmc_set_ranked_tuning gives one;
+  // an individual alone may take 1.5 KL times that (its lists against its
+  // values, which fit the value store), past which the call is HMC_ENOMEM.
+  // Rows are the caller's, output buffers the draws' with k draws.
+  int ranked_phasings(int64_t n, const int32_t *indiv, int k, int32_t *hap, double *prob, int32_t *count, int32_t *status);
+  int ranked_group(const ExactArgs &x, const int32_t *ids, int k, int dev_cu);
+  DrawCall rk;                     // the running call (draws = k)
+  std::vector<int32_t> rk_count;   // [shard] rows found
+  DevBuf<uint8_t> d_rk_store;
+  DevBuf<unsigned long long> d_rk_base, d_rk_total;
+  DevBuf<int32_t> d_rk_count;
+  uint64_t rk_store_bytes = 0;     // hmc_set_ranked_tuning (test seam): the list store's budget, 0 = the value store's
+  uint64_t rank_budget_bytes() const { return rk_store_bytes ? rk_store_bytes : trace_budget * 4; }
+  // of the last call, as mp_* above; rk_built: the list width KL of the kernel that ran; rk_batches: launches
+  double rk_ms_struct = 0, rk_ms_fb = 0, rk_ms_sweep = 0;
+  int rk_groups = 0, rk_pruned = 0, rk_built = 0, rk_batches = 0;
   DevBuf<unsigned long long> d_site_off;
   DevBuf<int32_t> d_site_locus, d_site_status;
   DevBuf<double> d_site_post;

@@ -200,7 +200,7 @@ int Ctx::exact_group(const int32_t *ids, int k, const std::function<int(std::vec
   x.head_al = d_head_al.p;
   x.acc_freq = d_xacc.p;
   x.acc_prefix = d_xacc.p + xacc_nc;
-  x.forward_only = (xp_mode == XP_DRAW && dr_forward_only) || xp_mode == XP_LIK || xp_mode == XP_MAP;
+  x.forward_only = (xp_mode == XP_DRAW && dr_forward_only) || xp_mode == XP_LIK || xp_mode == XP_MAP || xp_mode == XP_RANK;
   // extended range: the posterior calls when asked for, the likelihoods always, the exact M-step never
   x.extended = xp_mode == XP_LIK || (xp_mode != XP_OFF && xp_extended);
   if (x.extended) {
@@ -263,6 +263,7 @@ int Ctx::exact_group(const int32_t *ids, int k, const std::function<int(std::vec
   if (xp_mode == XP_DRAW) return draw_group(x, ids, k, dev_cu);
   if (xp_mode == XP_DOSE) return dosage_group(x, ids, fm, k, dev_cu);
   if (xp_mode == XP_MAP) return map_group(x, ids, k, dev_cu);
+  if (xp_mode == XP_RANK) return ranked_group(x, ids, k, dev_cu);
   if (xp_mode == XP_LIK) {  // the scaled totals of the group's individuals: nothing runs after exact_fb
     std::vector<double> tot(n);
     std::vector<int32_t> ex(n);
@@ -756,6 +757,113 @@ int Ctx::map_group(const ExactArgs &x, const int32_t *ids, int k, int dev_cu) {
   return HMC_OK;
 }
 
+int Ctx::ranked_group(const ExactArgs &x, const int32_t *ids, int k, int dev_cu) {
+  const int L = pan.L, A = pan.amax, K = rk.draws, KL = rank_width(K);
+  std::vector<int32_t> sel;  // the group's individuals that the caller asked for
+  for (int q = 0; q < k; ++q)
+    if (rk.row_off[ids[q] + 1] > rk.row_off[ids[q]]) sel.push_back(ids[q]);
+  if (sel.empty()) return HMC_OK;
+  const size_t per = (size_t)2 * L * K;  // haplotype entries of one individual
+  const size_t out_cap = std::max<size_t>(1, DRAW_OUT_BYTES / ((size_t)K * 8 + (rk.hap ? per * 5 : 0)));
+  hipError_t e;
+  int rc;
+  std::vector<int32_t> symtab((size_t)L * A, -1);  // the panel's symbol table, [locus][allele index]
+  for (int l = 0; l < L; ++l)
+    for (size_t j = 0; j < pan.sym[l].size(); ++j) symtab[(size_t)l * A + j] = pan.sym[l][j].first;
+  if (rk.hap &&
+      ((e = d_dr_sym.ensure(symtab.size())) ||
+       (e = hipMemcpyAsync(d_dr_sym.p, symtab.data(), symtab.size() * 4, hipMemcpyHostToDevice, st))))
+    return hipfail(e, "exact_ranked_phasings");
+  // the list store every individual needs: 24 KL bytes per state of its records and 8 per record
+  const int ns = (int)sel.size();
+  std::vector<unsigned long long> need(ns);
+  {
+    ExactArgs xt = x;
+    if ((e = d_dr_order.ensure(ns)) || (e = d_rk_total.ensure(ns))) return hipfail(e, "exact_ranked_phasings");
+    if ((rc = upload_order(d_dr_order, sel.data(), ns))) return rc;
+    xt.order = d_dr_order.p;
+    xt.n_order = ns;
+    if ((e = launch_exact_state_totals(xt, d_rk_total.p, st)) ||
+        (e = hipMemcpyAsync(need.data(), d_rk_total.p, (size_t)ns * 8, hipMemcpyDeviceToHost, st)) || (e = sync_st()))
+      return hipfail(e, "exact_ranked_phasings");
+    for (int u = 0; u < ns; ++u) need[u] = rank_store_bytes(KL, need[u], L + 1 - head_len);
+  }
+  // An individual's lists are 1.5 KL times its values, which fit the value store: alone in a batch it may take
+  // that multiple of the budget, so that no individual the forward pass held is refused for its lists.
+  const uint64_t budget = rank_budget_bytes(), alone = budget / 2 * 3 * (uint64_t)KL;
+  std::vector<int32_t> h_st, h_cnt, h_hap;
+  std::vector<double> h_prob;
+  std::vector<unsigned long long> sbase;
+  for (size_t pos = 0; pos < sel.size();) {
+    // a batch: individuals in order while their lists fit the budget (and the outputs theirs)
+    uint64_t bytes = 0;
+    int nb = 0;
+    sbase.clear();
+    while (pos + nb < sel.size() && (size_t)nb < out_cap && (nb == 0 || bytes + need[pos + nb] <= budget)) {
+      if (need[pos + nb] > alone)
+        return fail(HMC_ENOMEM, "ranked phasings: the lists of individual %d need %llu bytes at width %d (list store budget %llu)",
+                    i0 + sel[pos + nb], (unsigned long long)need[pos + nb], KL, (unsigned long long)budget);
+      sbase.push_back(bytes);
+      bytes += need[pos + nb];
+      ++nb;
+    }
+    const int grid = std::max(1, std::min(nb, dev_cu * 8));
+    ExactArgs xb = x;
+    RankArgs s;
+    if ((e = d_dr_order.ensure(nb)) || (e = d_dr_status.ensure(nb)) || (e = d_rk_count.ensure(nb)) || (e = d_rk_base.ensure(nb)) ||
+        (e = d_dr_prob.ensure((size_t)nb * K)) || (e = d_rk_store.ensure(std::max<size_t>(bytes, 8))) ||
+        (rk.hap && (e = d_dr_al.ensure((size_t)nb * per))) || (rk.hap && (e = d_dr_hap.ensure((size_t)nb * per))) ||
+        (e = hipMemsetAsync(d_dr_status.p, 0, (size_t)nb * 4, st)) ||  // the kernel writes the non-zero ones
+        (e = hipMemsetAsync(d_rk_count.p, 0, (size_t)nb * 4, st)) ||
+        (e = hipMemsetAsync(d_dr_prob.p, 0, (size_t)nb * K * 8, st)) ||  // rows past an individual's count: prob 0
+        (rk.hap && (e = hipMemsetAsync(d_dr_al.p, 0xFF, (size_t)nb * per, st))) ||
+        (e = hipMemcpyAsync(d_rk_base.p, sbase.data(), (size_t)nb * 8, hipMemcpyHostToDevice, st)))
+      return hipfail(e, "exact_ranked_phasings");
+    if ((rc = upload_order(d_dr_order, sel.data() + pos, nb))) return rc;
+    xb.order = d_dr_order.p;
+    xb.n_order = nb;
+    s.k = K;
+    s.al = rk.hap ? d_dr_al.p : nullptr;
+    s.prob = d_dr_prob.p;
+    s.count = d_rk_count.p;
+    s.status = d_dr_status.p;
+    s.store = d_rk_store.p;
+    s.store_base = d_rk_base.p;
+    hipEventRecord(ev[0], st);
+    if ((e = launch_exact_ranked_phasings(xb, s, KL, grid, st))) return hipfail(e, "exact_ranked_phasings");
+    if (rk.hap && (e = launch_draws_to_symbols(d_dr_al.p, d_dr_sym.p, d_dr_hap.p, nb, L, K, A, st)))
+      return hipfail(e, "draws_to_symbols");
+    hipEventRecord(ev[1], st);
+    h_st.resize(nb);
+    h_cnt.resize(nb);
+    h_prob.resize((size_t)nb * K);
+    h_hap.resize(rk.hap ? (size_t)nb * per : 0);
+    if ((e = hipMemcpyAsync(h_st.data(), d_dr_status.p, (size_t)nb * 4, hipMemcpyDeviceToHost, st)) ||
+        (e = hipMemcpyAsync(h_cnt.data(), d_rk_count.p, (size_t)nb * 4, hipMemcpyDeviceToHost, st)) ||
+        (e = hipMemcpyAsync(h_prob.data(), d_dr_prob.p, (size_t)nb * K * 8, hipMemcpyDeviceToHost, st)) ||
+        (rk.hap && (e = hipMemcpyAsync(h_hap.data(), d_dr_hap.p, (size_t)nb * per * 4, hipMemcpyDeviceToHost, st))) ||
+        (e = sync_st()))
+      return hipfail(e, "exact_ranked_phasings");
+    float ms = 0;
+    hipEventElapsedTime(&ms, ev[0], ev[1]);
+    xp_ms_sites += ms;
+    ++rk_batches;
+    for (int u = 0; u < nb; ++u) {
+      const int bi = sel[pos + u];
+      rk.status[bi] = h_st[u];
+      if (h_st[u] != 0) continue;  // (the caller's rows get the input genotype)
+      rk_count[bi] = h_cnt[u];
+      for (int64_t w = rk.row_off[bi]; w < rk.row_off[bi + 1]; ++w) {
+        const int64_t row = rk.rows[w];
+        if (rk.prob) std::copy(h_prob.begin() + (size_t)u * K, h_prob.begin() + (size_t)(u + 1) * K, rk.prob + (size_t)row * K);
+        if (rk.hap) std::copy(h_hap.begin() + (size_t)u * per, h_hap.begin() + (size_t)(u + 1) * per, rk.hap + (size_t)row * per);
+      }
+    }
+    pos += (size_t)nb;
+  }
+  return HMC_OK;
+}
+
 int Ctx::dosage_group(const ExactArgs &x, const int32_t *ids, const std::vector<int32_t> &fm, int k, int dev_cu) {
   const int NS = ds_ns_run, P = ds.P;
   std::vector<int32_t> sel;  // the group's individuals that the caller asked for
@@ -1040,6 +1148,75 @@ int Ctx::map_phase(int64_t n, const int32_t *indiv, int32_t *hap, double *prob, 
       for (int side = 0; side < 2; ++side)
         for (int l = 0; l < L; ++l)
           hap[((size_t)q * 2 + side) * L + l] = pan.symbol(l, pan.idx[((size_t)(i0 + i) * 2 + side) * L + l]);
+  }
+  return HMC_OK;
+}
+
+int Ctx::ranked_phasings(int64_t n, const int32_t *indiv, int k, int32_t *hap, double *prob, int32_t *count, int32_t *status) {
+  if (!have_estep) return fail(HMC_EARG, "ranked phasings need an E-step first (hmc_resolve_all)");
+  if (estep_gen != model_gen)
+    return fail(HMC_EARG, "ranked phasings: the model changed since the last E-step (hmc_resolve_all again)");
+  if (pan.amax > 44) return fail(HMC_EUNSUPPORTED, "ranked phasings with more than 44 alleles per locus");
+  if (k < 1 || k > RANK_K_MAX) return fail(HMC_EARG, "ranked phasings: k = %d is outside [1, %d]", k, RANK_K_MAX);
+  const int nl = nloc(), L = pan.L;
+  if (!indiv) n = nl;
+  if (n < 0) return fail(HMC_EARG, "ranked phasings: n = %lld is negative", (long long)n);
+  for (int64_t q = 0; indiv && q < n; ++q)
+    if (indiv[q] < i0 || indiv[q] >= i1)
+      return fail(HMC_EARG, "ranked phasings: entry %lld: individual %d is outside this rank's shard [%d, %d)", (long long)q,
+                  indiv[q], i0, i1);
+  rk_ms_struct = rk_ms_fb = rk_ms_sweep = 0;
+  rk_groups = rk_pruned = rk_built = rk_batches = 0;
+  if (n == 0) return HMC_OK;
+  auto local = [&](int64_t q) { return indiv ? indiv[q] - i0 : (int)q; };
+  rk.draws = k;
+  rk.hap = hap;
+  rk.prob = prob;
+  rk.row_off.assign((size_t)nl + 1, 0);
+  for (int64_t q = 0; q < n; ++q) ++rk.row_off[local(q) + 1];
+  for (int i = 0; i < nl; ++i) rk.row_off[i + 1] += rk.row_off[i];
+  rk.rows.assign((size_t)n, 0);
+  {
+    std::vector<int64_t> at(rk.row_off.begin(), rk.row_off.end() - 1);
+    for (int64_t q = 0; q < n; ++q) rk.rows[at[local(q)]++] = q;
+  }
+  rk.status.assign(nl, 1);
+  rk_count.assign(nl, 0);
+  hipError_t er;
+  if ((er = d_xstatus.ensure(nl)) || (er = d_xre.ensure(nl)) || (er = d_xfmax.ensure(nl))) return hipfail(er, "ranked phasings");
+  // the pass counts in the genotype posteriors' fields: theirs are put back
+  const double g_struct = xp_ms_struct, g_fb = xp_ms_fb, g_sites = xp_ms_sites;
+  const int g_groups = xp_groups, g_pruned = xp_pruned;
+  std::vector<char> asked(nl, 0);  // the passes run over the individuals asked for, not the whole shard
+  for (int i = 0; i < nl; ++i) asked[i] = rk.row_off[i + 1] > rk.row_off[i];
+  const int rc = xp_pass(XP_RANK, "ranked phasings", &asked);
+  rk_ms_struct = xp_ms_struct;
+  rk_ms_fb = xp_ms_fb;
+  rk_ms_sweep = xp_ms_sites;
+  rk_groups = xp_groups;
+  rk_pruned = xp_pruned;
+  rk_built = rank_width(k);
+  xp_ms_struct = g_struct;
+  xp_ms_fb = g_fb;
+  xp_ms_sites = g_sites;
+  xp_groups = g_groups;
+  xp_pruned = g_pruned;
+  rk.hap = nullptr;
+  rk.prob = nullptr;
+  if (rc) return rc;
+  for (int64_t q = 0; q < n; ++q) {
+    const int i = local(q), stt = rk.status[i], cnt = stt == 0 ? rk_count[i] : 0;
+    if (status) status[q] = stt;
+    if (count) count[q] = cnt;
+    // rows past the count (all of them for an unresolved individual or a subnormal P(genotype)): the input
+    // genotype, as hmc_get_resolutions gives it, at probability 0
+    for (int r = cnt; r < k; ++r) {
+      if (prob) prob[(size_t)q * k + r] = 0.0;
+      if (hap)
+        for (int side = 0; side < 2; ++side)
+          for (int l = 0; l < L; ++l)
+            hap[(((size_t)q * k + r) * 2 + side) * L + l] = pan.symbol(l, pan.idx[((size_t)(i0 + i) * 2 + side) * L + l]);
+    }
   }
   return HMC_OK;
 }

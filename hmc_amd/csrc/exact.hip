@@ -2306,4 +2306,309 @@ hipError_t launch_exact_map_phase(const ExactArgs &a, const MapArgs &s, int grid
   return hipGetLastError();
 }
 
+// Ranked phasings (hmc_ranked_phasings): the k haplotype pairs of largest
+// exact posterior, each once, with its posterior — exact_map_phase from
+// max-product to list max-product.  State t of a record keeps two descending
+// lists of at most KL values, Lh[t] (haplotypes equal so far) and Ld[t]
+// (already different, the pair factor 2 inside); empty slots are 0.
+//   Head record: homozygous state Lh = (tpv), Ld = (); heterozygous Lh = (),
+//   Ld = (tpv * 2.0).
+//   Record j above it, state t with alleles (xa, xb), contributions r in
+//   record order, p = pred(r), primes for record j - 1; the candidates are
+//     xa == xb   Lh[t]: (Lh'[p][q], key (r, q));  Ld[t]: (Ld'[p][q], key (r, q))
+//     else       Lh[t] empty;  Ld[t]: (Ld'[p][q], key (r, 0, q)) and
+//                (2.0 * Lh'[p][q], key (r, 1, q)) — the latter unless an
+//                earlier contribution of t names the same predecessor p.
+//   A heterozygous pair behind a homozygous prefix is two mirror paths of half
+//   each (rev or not out of the state both haplotypes share); paths whose
+//   haplotypes are equal so far share their contexts, so the two mirrors are
+//   the two contributions of t from one predecessor, and the 2 h candidates of
+//   the second would list every such pair twice.  (Ld' is read from both: once
+//   the haplotypes differ the two orientations are two pairs.)
+//   Candidates by value descending, then key ascending; the first KL with a
+//   value > 0 are kept and then multiplied by tpv[t], one multiplication each.
+//   The candidates arrive in key order and a predecessor's list is sorted, so
+//   a list is left at its first entry that cannot enter (not above the running
+//   KL-th value: an equal value with a later key loses).
+// Every record is rescaled (rescale_record over its 2 F KL values); its
+// largest value is a rank-0 entry, which is exact_map_phase's maximum, so the
+// exponents and the rank-0 values are those of its rescaled sweep.
+// The list store, of this call alone (the forward pass's x-store holds 2 F
+// doubles per record): per individual from RankArgs::store_base, record j at
+// 24 KL (states of the records below) + 8 (j - head_len) bytes — values
+// [F][2][KL] doubles, back-pointers [F][2][KL] words (contribution offset in
+// the state's range << 5 | source label d << 4 | source rank), the cumulative
+// exponent and a pad word.  The states below a record come from the forward
+// pass's x_off, which counts 4 F + 2 words per record.
+//   Final record: candidates (t, label, q), key (2 t + label, q), the same
+//   order; the first k are the rows — one block reduction per row, each taking
+//   the first candidate behind the previous row's.
+//   Traceback: lane r of wave 0 follows row r down its back-pointers; spelling
+//   and prob exactly as exact_map_phase.  Neither the block size nor KL enters.
+template <int KL>
+__device__ inline void rank_insert(double (&v)[KL], uint32_t (&b)[KL], double x, uint32_t xb) {  // x > v[KL - 1]
+#pragma unroll
+  for (int i = KL - 1; i >= 0; --i) {
+    if (v[i] < x) {  // entry i moves down; x lands here if the entry above stays
+      const bool shift = i > 0 && v[i > 0 ? i - 1 : 0] < x;
+      v[i] = shift ? v[i > 0 ? i - 1 : 0] : x;
+      b[i] = shift ? b[i > 0 ? i - 1 : 0] : xb;
+    }
+  }
+}
+
+// the candidates of one predecessor list, x = scale * pv[q], into the running list
+template <int KL>
+__device__ inline void rank_take(double (&v)[KL], uint32_t (&b)[KL], const double *pv, double scale, uint32_t code) {
+  for (int q = 0; q < KL; ++q) {
+    const double x = scale * pv[q];
+    if (!(x > v[KL - 1])) break;
+    rank_insert<KL>(v, b, x, code | (uint32_t)q);
+  }
+}
+
+__device__ inline size_t rank_rec_offset(const unsigned long long *xo, int hl, int j, int KL) {  // bytes from the individual's base
+  const unsigned long long below = (xo[j] - xo[hl] - 2ull * (unsigned)(j - hl)) / 4ull;  // states of records hl .. j - 1
+  return (size_t)24 * KL * below + (size_t)8 * (j - hl);
+}
+
+template <int KL, bool EXT>
+__global__ __launch_bounds__(256) void exact_ranked_phasings(ExactArgs a, RankArgs s) {
+  __shared__ double bv[2][4];
+  __shared__ unsigned bk[2][4];
+  const int tid = threadIdx.x, NT = blockDim.x, lane = tid & (WAVE - 1), wave = tid / WAVE, nw = NT / WAVE;
+  const int L = a.L, hl = a.head_len, K = s.k;
+  for (int q = blockIdx.x; q < a.n_order; q += gridDim.x) {  // block-uniform
+    const int bi = a.order[q];
+    const int st0 = a.status[bi];
+    const double pg = EXT ? a.xtot[bi] : a.gprob[bi];
+    const int pge = EXT ? -a.xtot_exp[bi] : 0;  // P(genotype) = pg 2^pge
+    const bool resolved = (st0 == EST_OK || st0 == EST_OK_PRUNED) && pg > 0.0 && !isinf(pg);
+    if (!resolved || (!EXT && pg < SITE_PG_MIN)) {  // the host writes the input genotype: unresolved (1), P(genotype) subnormal (2)
+      if (tid == 0) s.status[q] = resolved ? 2 : 1;
+      continue;
+    }
+    const unsigned long long *roff = a.rec_off + (size_t)bi * (L + 1);
+    const unsigned long long *xo = a.x_off + (size_t)bi * (L + 1);
+    uint8_t *base = s.store + s.store_base[q];
+    // ---- the sweep -------------------------------------------------------
+    int ex = 0;
+    {
+      const RecView R(a.rec + roff[hl], true);
+      double *vals = (double *)(base + rank_rec_offset(xo, hl, hl, KL));
+      double m = 0.0;
+      for (int t = tid; t < R.F; t += NT) {
+        const bool homo = (R.hdr[t] >> 24) & 1u;
+        const double tpv = R.tpv[t];
+        double *o = vals + (size_t)t * 2 * KL;
+#pragma unroll
+        for (int i = 0; i < 2 * KL; ++i) o[i] = 0.0;
+        const double v = homo ? tpv : tpv * 2.0;
+        o[homo ? 0 : KL] = v;
+        m = fmax(m, v);
+      }
+      ex += rescale_record(vals, 2 * R.F * KL, m);
+      if (tid == 0) ((int32_t *)(vals + (size_t)3 * R.F * KL))[0] = ex;
+    }
+    for (int j = hl + 1; j <= L; ++j) {
+      const RecView R(a.rec + roff[j], false);
+      const double *pvals = (const double *)(base + rank_rec_offset(xo, hl, j - 1, KL));
+      double *vals = (double *)(base + rank_rec_offset(xo, hl, j, KL));
+      uint32_t *bps = (uint32_t *)(vals + (size_t)2 * R.F * KL);
+      double m = 0.0;
+      for (int t = tid; t < R.F; t += NT) {
+        const uint32_t hd = R.hdr[t];
+        const bool homo = (hd & 0xFFu) == ((hd >> 8) & 0xFFu);
+        double lh[KL], ld[KL];
+        uint32_t bh[KL], bd[KL];
+#pragma unroll
+        for (int i = 0; i < KL; ++i) {
+          lh[i] = ld[i] = 0.0;
+          bh[i] = bd[i] = 0u;
+        }
+        const uint32_t r0 = R.cb[t], r1 = R.cb[t + 1];
+        for (uint32_t r = r0; r < r1; ++r) {
+          const uint32_t p = cw_state(R.ct[r]);
+          const double *pv = pvals + (size_t)p * 2 * KL;
+          const uint32_t code = (r - r0) << 5;
+          if (homo) {
+            rank_take<KL>(lh, bh, pv, 1.0, code);
+            rank_take<KL>(ld, bd, pv + KL, 1.0, code | 16u);
+          } else {
+            rank_take<KL>(ld, bd, pv + KL, 1.0, code | 16u);
+            if (2.0 * pv[0] > ld[KL - 1]) {  // (h values are rare: only states whose two contexts are one)
+              bool mirror = false;
+              for (uint32_t e = r0; e < r; ++e) mirror |= cw_state(R.ct[e]) == p;
+              if (!mirror) rank_take<KL>(ld, bd, pv, 2.0, code);
+            }
+          }
+        }
+        const double tpv = R.tpv[t];
+        double *o = vals + (size_t)t * 2 * KL;
+        uint32_t *ob = bps + (size_t)t * 2 * KL;
+#pragma unroll
+        for (int i = 0; i < KL; ++i) {
+          o[i] = homo ? tpv * lh[i] : 0.0;
+          o[KL + i] = tpv * ld[i];
+          ob[i] = bh[i];
+          ob[KL + i] = bd[i];
+        }
+        m = fmax(m, fmax(homo ? tpv * lh[0] : 0.0, tpv * ld[0]));
+      }
+      ex += rescale_record(vals, 2 * R.F * KL, m);
+      if (tid == 0) ((int32_t *)(vals + (size_t)3 * R.F * KL))[0] = ex;
+    }
+    // ---- the final record's first K candidates: row r in lane r of every wave
+    const RecView RL(a.rec + roff[L], L == hl);
+    const double *vL = (const double *)(base + rank_rec_offset(xo, hl, L, KL));
+    double pv = 0.0;
+    unsigned pk = 0u, rowk = 0u;
+    int cnt = 0;
+    for (int r = 0; r < K; ++r) {  // block-uniform
+      double best = -1.0;
+      unsigned bkey = 0xFFFFFFFFu;
+      for (int t = tid; t < RL.F; t += NT) {  // keys ascending: strictly larger only
+        for (int lab = 0; lab < 2; ++lab) {
+          const double *l = vL + ((size_t)t * 2 + lab) * KL;
+          for (int i = 0; i < KL; ++i) {
+            const double v = l[i];
+            if (!(v > 0.0)) break;
+            const unsigned key = (2u * (unsigned)t + (unsigned)lab) * KL + (unsigned)i;
+            if (r == 0 || v < pv || (v == pv && key > pk)) {  // the list's first entry behind the previous row
+              if (v > best) {
+                best = v;
+                bkey = key;
+              }
+              break;
+            }
+          }
+        }
+      }
+      wave_best(best, bkey);
+      if (lane == 0) {
+        bv[r & 1][wave] = best;
+        bk[r & 1][wave] = bkey;
+      }
+      __syncthreads();  // (the other buffer is rewritten only behind the next row's barrier)
+      best = bv[r & 1][0];
+      bkey = bk[r & 1][0];
+      for (int w = 1; w < nw; ++w)
+        if (bv[r & 1][w] > best || (bv[r & 1][w] == best && bk[r & 1][w] < bkey)) {
+          best = bv[r & 1][w];
+          bkey = bk[r & 1][w];
+        }
+      if (!(best > 0.0)) break;
+      pv = best;
+      pk = bkey;
+      if (lane == r) rowk = bkey;
+      ++cnt;
+    }
+    if (wave != 0) continue;  // (wave 0 passes the next individual's barriers after its tracebacks)
+    if (lane == 0) {
+      if (s.count) s.count[q] = cnt;
+      if (cnt == 0) s.status[q] = 1;  // (no path with a positive product: the host writes the input genotype)
+    }
+    const bool mine = lane < cnt;  // ---- traceback of row `lane` (no divergent way to the next individual's barriers)
+    auto put = [&](int locus, int side, uint32_t x) {
+      if (s.al) s.al[(((size_t)q * 2 + side) * L + locus) * K + lane] = (uint8_t)x;
+    };
+    int t = (int)(rowk / (2u * KL));
+    uint32_t lab = (rowk / KL) & 1u, rk = rowk % KL;
+    int par = 0;
+    bool het = false, dead = false;
+    double p = 1.0;
+    int pe = 0;  // the true product is p 2^pe
+    auto renorm = [&]() {
+      int e;
+      p = frexp(p, &e);
+      pe += e;
+    };
+    for (int j = L; mine && j > hl; --j) {
+      const RecView R(a.rec + roff[j], false);
+      const uint32_t hd = R.hdr[t], xa = hd & 0xFFu, xb = (hd >> 8) & 0xFFu;
+      const uint32_t r0 = R.cb[t], r1 = R.cb[t + 1];
+      const double tpv = R.tpv[t];
+      put(j - 1, par, xa);
+      put(j - 1, par ^ 1, xb);
+      het |= xa != xb;
+      p = j == L ? tpv : p * tpv;
+      renorm();
+      const uint32_t *bps = (const uint32_t *)(base + rank_rec_offset(xo, hl, j, KL) + (size_t)16 * R.F * KL);
+      const uint32_t bp = bps[((size_t)t * 2 + lab) * KL + rk];
+      const uint32_t r = r0 + (bp >> 5);
+      if (r >= r1 || (bp & 15u) >= (uint32_t)KL) {  // (never: an entry with a positive value has a contribution behind it)
+        dead = true;
+        break;
+      }
+      const uint32_t w = R.ct[r];
+      lab = (bp >> 4) & 1u;
+      rk = bp & 15u;
+      if (cw_rev(w)) par ^= 1;
+      t = (int)cw_state(w);
+    }
+    if (mine && !dead) {  // the head state: loci below head_len
+      const RecView H(a.rec + roff[hl], true);
+      const double tpv = H.tpv[t];
+      p = L == hl ? tpv : p * tpv;
+      renorm();
+      if (hl == 1) {
+        const uint32_t hd = H.hdr[t], xa = hd & 0xFFu, xb = (hd >> 8) & 0xFFu;
+        put(0, par, xa);
+        put(0, par ^ 1, xb);
+        het |= xa != xb;
+      } else {
+        const uint32_t *plo = H.cb + H.F + 1, *phi = plo + H.F;
+        const uint8_t *pa = a.head_al + (size_t)plo[t] * hl, *pb = a.head_al + (size_t)phi[t] * hl;
+        for (int k = 0; k < hl; ++k) {
+          put(k, par, pa[k]);
+          put(k, par ^ 1, pb[k]);
+          het |= pa[k] != pb[k];
+        }
+      }
+    }
+    if (mine && s.prob) s.prob[(size_t)q * K + lane] = dead ? 0.0 : ldexp((het ? p * 2.0 : p) / pg, pe - pge);
+  }
+}
+
+// total states of the records of every individual of the group (what sizes its list store)
+__global__ void exact_state_totals(ExactArgs a, unsigned long long *total) {
+  const int q = blockIdx.x * blockDim.x + threadIdx.x;
+  if (q >= a.n_order) return;
+  const int bi = a.order[q], L = a.L, hl = a.head_len;
+  const int st0 = a.status[bi];
+  if (st0 != EST_OK && st0 != EST_OK_PRUNED) {  // (exact_fb laid out no x_off: the kernel leaves the individual at once)
+    total[q] = 0;
+    return;
+  }
+  const unsigned long long *xo = a.x_off + (size_t)bi * (L + 1);
+  total[q] = (xo[L] - xo[hl] - 2ull * (unsigned)(L - hl)) / 4ull + a.rec[a.rec_off[(size_t)bi * (L + 1) + L]];
+}
+
+hipError_t launch_exact_state_totals(const ExactArgs &a, unsigned long long *total, hipStream_t st) {
+  if (a.n_order <= 0) return hipSuccess;
+  if (!total) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(exact_state_totals, dim3((a.n_order + 255) / 256), dim3(256), 0, st, a, total);
+  return hipGetLastError();
+}
+
+template <int KL>
+static hipError_t launch_ranked(const ExactArgs &a, const RankArgs &s, int grid, hipStream_t st, int block) {
+  if (a.extended) hipLaunchKernelGGL((exact_ranked_phasings<KL, true>), dim3(grid), dim3(block), 0, st, a, s);
+  else hipLaunchKernelGGL((exact_ranked_phasings<KL, false>), dim3(grid), dim3(block), 0, st, a, s);
+  return hipGetLastError();
+}
+
+hipError_t launch_exact_ranked_phasings(const ExactArgs &a, const RankArgs &s, int kl, int grid, hipStream_t st, int block) {
+  if (a.n_order <= 0) return hipSuccess;
+  if (grid < 1 || !s.status || !s.store || !s.store_base || s.k < 1 || s.k > kl || block < WAVE || block > 256 || block % WAVE)
+    return hipErrorInvalidValue;
+  switch (kl) {
+    case 2: return launch_ranked<2>(a, s, grid, st, block);
+    case 4: return launch_ranked<4>(a, s, grid, st, block);
+    case 8: return launch_ranked<8>(a, s, grid, st, block);
+    case 16: return launch_ranked<16>(a, s, grid, st, block);
+  }
+  return hipErrorInvalidValue;  // a width that is not built is an error, never another kernel
+}
+
 }  // namespace hmc

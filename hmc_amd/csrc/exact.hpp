@@ -242,4 +242,39 @@ struct MapArgs {
 // after exact_fb (forward only will do) over the same group; block sizes 64 .. 256 and the grid do not change the bits
 hipError_t launch_exact_map_phase(const ExactArgs &a, const MapArgs &s, int grid, hipStream_t st, int block = 256);
 
+// Ranked phasings (exact_ranked_phasings): the k haplotype pairs of largest
+// exact posterior of every individual of the group, each once, by a list
+// max-product sweep (two descending lists of KL values per state, KL >= k the
+// list width the kernel was built with) and k tracebacks in the same launch.
+// The lists do not fit the x-store, which exact_fb's forward-only pass over the
+// same group has laid out (x_off; read for the states per record) and which
+// keeps its forward values: the sweep has a store of its own, per individual
+// rank_store_bytes(kl, states, records) from store_base[slot], record j of
+// F states as values [F][2][KL] doubles, back-pointers [F][2][KL] words, the
+// record's cumulative exponent and a pad word.
+// Individual q of the group (ExactArgs::order) owns output slot q; al in
+// DrawArgs' layout with draws = k, al[slot][side][locus][row] bytes (may be
+// NULL); rows at and past count[slot] are left unwritten; status is zeroed by
+// the caller: the kernel writes the non-zero ones only.
+struct RankArgs {
+  int k = 0;                       // rows per individual, 1 .. KL
+  uint8_t *al = nullptr;           // [slots][2][L][k] allele indices
+  double *prob = nullptr;          // [slots][k]
+  int32_t *count = nullptr;        // [slots] rows written
+  int32_t *status = nullptr;       // [slots] 0 ok, 1 unresolved, 2 P(genotype) subnormal
+  uint8_t *store = nullptr;        // the list store
+  const unsigned long long *store_base = nullptr;  // [slots] byte offsets into it (multiples of 8)
+};
+constexpr int RANK_K_MAX = 16;
+// the smallest list width that is built and holds k rows (2, 4, 8, 16)
+constexpr int rank_width(int k) { return k <= 2 ? 2 : k <= 4 ? 4 : k <= 8 ? 8 : 16; }
+// list store of one individual with `states` states over `records` records
+constexpr unsigned long long rank_store_bytes(int kl, unsigned long long states, int records) {
+  return 24ull * (unsigned)kl * states + 8ull * (unsigned)records;
+}
+// total[q] = the states of all records of individual q of the group (0 for one exact_fb skipped); after exact_fb
+hipError_t launch_exact_state_totals(const ExactArgs &a, unsigned long long *total, hipStream_t st);
+// after exact_fb (forward only will do) over the same group; kl, block sizes 64 .. 256 and the grid do not change the bits
+hipError_t launch_exact_ranked_phasings(const ExactArgs &a, const RankArgs &s, int kl, int grid, hipStream_t st, int block = 256);
+
 }  // namespace hmc

@@ -733,6 +733,48 @@ class HaploModel:
         """map_phase of the whole shard as text, three lines per individual (hmc_write_map_phase)."""
         self._check(lib().hmc_write_map_phase(self._h, path.encode()))
 
+    def ranked_phasings(self, k: int, indiv=None) -> dict:
+        """The k most probable haplotype pairs under the model of the last
+        resolve_all, each once, with their exact posteriors
+        (hmc_ranked_phasings; 1 <= k <= 16): for the panel indices `indiv`
+        (any order, repeats allowed; None = this rank's whole shard)
+        hap[n, k, 2, L] symbols, prob[n, k] descending, count[n] rows found,
+        status[n] as map_phase.  Rows at and past count carry the input
+        genotype at prob 0.  Row 0 is map_phase()'s answer byte for byte, and
+        row r is the same for every k > r."""
+        if indiv is None:
+            qi, n = None, self.i1 - self.i0
+        else:
+            qi = np.ascontiguousarray(indiv, np.int32).reshape(-1)
+            n = len(qi)
+        kk = max(int(k), 0)
+        out = dict(hap=np.zeros((n, kk, 2, self.L), np.int32), prob=np.zeros((n, kk), np.float64),
+                   count=np.zeros(n, np.int32), status=np.zeros(n, np.int32))
+        self._check(lib().hmc_ranked_phasings(self._h, n, None if qi is None else _p(qi, C.c_int32), int(k),
+                                              _p(out["hap"], C.c_int32), _p(out["prob"], C.c_double),
+                                              _p(out["count"], C.c_int32), _p(out["status"], C.c_int32)))
+        return out
+
+    def ranked_stats(self) -> dict:
+        """Device ms and counts of the last ranked_phasings (hmc_last_ranked_stats);
+        k_built: the list width of the kernel that ran; batches: its launches."""
+        s, f, w = C.c_double(), C.c_double(), C.c_double()
+        g, p, b, nb = C.c_int(), C.c_int(), C.c_int(), C.c_int()
+        self._check(lib().hmc_last_ranked_stats(self._h, C.byref(s), C.byref(f), C.byref(w), C.byref(g), C.byref(p), C.byref(b)))
+        self._check(lib().hmc_last_ranked_batches(self._h, C.byref(nb)))
+        return dict(structure_ms=s.value, fb_ms=f.value, sweep_ms=w.value, groups=g.value, n_pruned=p.value,
+                    k_built=b.value, batches=nb.value)
+
+    def set_ranked_tuning(self, store_bytes: int = 0):
+        """Test seam: the budget of ranked_phasings' list store in bytes (0 =
+        the value store's budget); a small one sends a group's individuals
+        through several launches.  No result depends on it."""
+        self._check(lib().hmc_set_ranked_tuning(self._h, int(store_bytes)))
+
+    def write_ranked_phasings(self, path: str, k: int = 4):
+        """ranked_phasings of the whole shard as text, one line per individual and rank (hmc_write_ranked_phasings)."""
+        self._check(lib().hmc_write_ranked_phasings(self._h, path.encode(), int(k)))
+
     def set_posterior_range(self, extended: bool):
         """Range of genotype_posteriors, switch_posteriors, pair_posteriors,
         posterior_draws and their write_* forms (hmc_set_posterior_range).

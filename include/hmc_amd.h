@@ -564,9 +564,103 @@ int hmc_map_phase(hmc_ctx *ctx, int64_t n, const int32_t *indiv, int32_t *hap, d
  * groups the individuals ran in; individuals on pruned records.  Replaces no
  * reference interface. */
 int hmc_last_map_stats(const hmc_ctx *ctx, double *structure_ms, double *fb_ms, double *sweep_ms, int *groups, int *n_pruned);
+/* Ranked phasings: the k haplotype pairs of largest exact posterior P(pair |
+ * genotype) under the model of the last E-step, each once, with its posterior
+ * — what "MAP pair, posterior 0.41" leaves open: the top diplotypes with their
+ * probabilities, whether the second-best phasing flips a call, how many
+ * phasings cover 95 %.  (The E-step's k-best list, hmc_get_estep /
+ * hmc_get_samples, is a beam cut at every locus and no exact ranking; a
+ * posterior draw finds the runners-up by luck and with repeats.)
+ * indiv[n] are panel indices inside this rank's shard, in any order, repeats
+ * allowed; indiv = NULL means the whole shard (n is ignored).  1 <= k <= 16.
+ * Outputs, any of which may be NULL: hap[n][k][2][L] symbols, prob[n][k],
+ * count[n], status[n].
+ *   Rows.  Row r of individual i is the pair of (r + 1)-th largest exact
+ *   posterior among *unordered* haplotype pairs; each pair is listed at most
+ *   once.
+ *   Count.  count[i] = min(k, the pairs whose computed value is positive);
+ *   rows r >= count[i] carry the input genotype (as hmc_get_resolutions gives
+ *   it for unresolved individuals) and prob 0.0.
+ *   Status 0 / 1 / 2 exactly where hmc_map_phase puts them; for status 1 and
+ *   2 count is 0 and every row is the input genotype at prob 0.
+ *   prob by the rule of hmc_map_phase and hmc_posterior_draws: tpv of the
+ *   final state times tpv of each chosen state down to the head record, one
+ *   multiplication each in that order, kept as mantissa and exponent, doubled
+ *   if the two haplotypes differ anywhere, divided by P(genotype) — a pair has
+ *   one number in this call, in hmc_map_phase and wherever a draw hits it.
+ *   Row 0 is hmc_map_phase's answer byte for byte (hap, prob, status), in both
+ *   ranges.
+ *   k does not enter: row r has the same bytes for every k > r.  Nor do the
+ *   other individuals of the call, sharding, launch shapes, store budgets,
+ *   groups, or the list width the kernel was built with.
+ *
+ * The sweep is hmc_map_phase's with lists in place of maxima.  Every state t
+ * of a record keeps two descending lists of at most K values (K the list
+ * width, at least k; empty slots are 0): Lh[t] over paths whose two haplotypes
+ * are equal so far, Ld[t] over paths that differ already, the pair factor 2
+ * inside.
+ *   Head record: a homozygous head state has Lh = (tpv), Ld = (); a
+ *   heterozygous one Lh = (), Ld = (tpv * 2.0).
+ *   Record j above it, state t with alleles (xa, xb), contributions r in
+ *   record order, p = pred(r), primes for record j - 1.  Candidates:
+ *     xa == xb, for Lh[t]:  (Lh'[p][q], key (r, q));
+ *     xa == xb, for Ld[t]:  (Ld'[p][q], key (r, q));
+ *     xa != xb:  Lh[t] is empty; for Ld[t] every r gives (Ld'[p][q], key
+ *       (r, 0, q)) and (2.0 * Lh'[p][q], key (r, 1, q)) — the latter unless an
+ *       earlier contribution of t names the same predecessor p.
+ *   The mirror.  A heterozygous pair behind a homozygous prefix is two mirror
+ *   paths of half each: out of the state that both haplotypes share, rev or
+ *   not.  For one value they tie and the first wins; in a list both would
+ *   appear, the same pair twice.  Paths whose haplotypes are equal so far share
+ *   their contexts, so the two mirrors are the two contributions of t that come
+ *   from one predecessor, and the 2 h candidates are taken from the first of
+ *   them only.  (Ld' is taken from both: once the haplotypes differ, the two
+ *   orientations are two different pairs.)
+ *   Order.  Candidates by value descending, then key ascending
+ *   lexicographically; the first K with a value > 0 are kept and then
+ *   multiplied by tpv[t], one multiplication per kept entry — after the
+ *   selection, so a power of two on a whole record changes no choice.
+ *   Final record: candidates (t, label, q) with key (2 t + label, q), h = 0
+ *   and d = 1, in the same order; the first k are the rows.
+ *   Traceback: every row goes down by the choice that produced its entry;
+ *   spelling (side parity, the rev flip after writing, the head state's loci)
+ *   and prob are hmc_map_phase's.
+ *   Scaling: every record's 2 F K values are multiplied by the power of two
+ *   that brings the record's largest into [0.5, 1), in both ranges.  That
+ *   largest value is a rank-0 entry, hmc_map_phase's maximum, so row 0 makes
+ *   hmc_map_phase's choices; an entry more than 2^1021 below its record's
+ *   maximum loses bits.
+ * At K = 1 these are hmc_map_phase's rules.  Two pairs whose computed values
+ * differ by less than the rounding of at most 2L + 2 operations may be listed
+ * in either order; no pair is listed twice and none of a larger computed
+ * value is skipped.
+ * Range (hmc_set_posterior_range) as for hmc_map_phase: regular divides by the
+ * last E-step's P(genotype) and gives status 2 where that is below DBL_MIN;
+ * extended divides by the scaled forward pass's own total and never gives
+ * status 2; individuals whose forward likelihood underflows are swept over the
+ * pruned records.
+ * Needs a preceding hmc_resolve_all (any E-step mode); runs its own exact-mode
+ * structure pass, forward pass and list sweep with the tracebacks, over the
+ * individuals asked for only, and changes no later result.  The lists live in
+ * a device store of this call's own, 24 K bytes per state and record, and the
+ * individuals go through in batches that fit the value store's budget
+ * (hmc_set_store_budgets); an individual alone may take 1.5 K times that
+ * budget (its lists against its values, which fit the value store), and
+ * HMC_ENOMEM names one whose lists exceed even that.  n = 0 is HMC_OK with no device work and zeroed stats.  HMC_EARG
+ * and HMC_EUNSUPPORTED as for hmc_map_phase; HMC_EARG also for k < 1 or
+ * k > 16.  Replaces no reference interface. */
+int hmc_ranked_phasings(hmc_ctx *ctx, int64_t n, const int32_t *indiv, int k, int32_t *hap, double *prob, int32_t *count,
+                        int32_t *status);
+/* Last hmc_ranked_phasings: device ms of its structure passes, of the forward
+ * kernel and of the list sweep with its tracebacks and transposition; groups
+ * the individuals ran in; individuals on pruned records; the list width of
+ * the kernel that ran (the smallest of 2, 4, 8, 16 that holds k).  Replaces no
+ * reference interface. */
+int hmc_last_ranked_stats(const hmc_ctx *ctx, double *structure_ms, double *fb_ms, double *sweep_ms, int *groups,
+                          int *n_pruned, int *k_built);
 /* Range of the posterior family (hmc_genotype_posteriors, hmc_switch_posteriors,
- * hmc_pair_posteriors, hmc_posterior_draws, hmc_map_phase and their
- * hmc_write_* forms).
+ * hmc_pair_posteriors, hmc_posterior_draws, hmc_map_phase,
+ * hmc_ranked_phasings and their hmc_write_* forms).
  * extended = 0 (default): the forward-backward pass keeps raw doubles and
  * divides by the last E-step's P(genotype); an individual whose P(genotype) is
  * below DBL_MIN gets status 2, one whose forward likelihood underflowed to 0
@@ -733,6 +827,15 @@ int hmc_write_posterior_draws(hmc_ctx *ctx, const char *path, int draws, uint64_
  * for a missing input allele in a row of status 1 or 2).  Needs a preceding
  * hmc_resolve_all or hmc_run.  Replaces no reference interface. */
 int hmc_write_map_phase(hmc_ctx *ctx, const char *path);
+/* hmc_ranked_phasings of the whole shard as text (hmc_resolve --output-ranked
+ * FILE --ranked K): the header "Id\tRank\tPosterior\tHaplotype0\tHaplotype1",
+ * then one line per individual of status 0 and per rank < count,
+ * individual-major: the id, the rank (from 0), the pair's posterior as %.17g
+ * (reads back to the same double) and the two haplotypes, tab-separated, each
+ * haplotype spelled as hmc_write_posterior_draws spells it.  Needs a preceding
+ * hmc_resolve_all or hmc_run; HMC_EARG for k < 1 or k > 16.  Replaces no
+ * reference interface. */
+int hmc_write_ranked_phasings(hmc_ctx *ctx, const char *path, int k);
 /* hmc_haplotype_dosages of the whole shard as text (hmc_resolve
  * --output-dosages FILE --haplotypes HAPFILE): the header
  * "Id\tHaplotype\tDosage", then one line per individual of status 0 and per

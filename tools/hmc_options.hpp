@@ -25,7 +25,10 @@ struct Options {
   std::string output_dosages;          // --output-dosages FILE
   std::string haplotypes;              // --haplotypes HAPFILE (required with it)
   std::string output_map;              // --output-map FILE
-  bool extended_range = false;         // --extended-range (needs one of the --output-*posteriors / --output-draws / --output-dosages / --output-map options)
+  std::string output_ranked;           // --output-ranked FILE
+  int ranked = 4;                      // --ranked K (1 .. 16)
+  bool have_ranked = false;
+  bool extended_range = false;         // --extended-range (needs one of the --output-*posteriors / --output-draws / --output-dosages / --output-map / --output-ranked options)
 };
 
 // --output-posteriors (no reference counterpart): <first file>.posteriors, the
@@ -62,7 +65,10 @@ constexpr const char *USAGE =
     "                        start the 0-based first locus, alleles as the genotype files spell them, ? = any)\n"
     "  --output-map FILE     write FILE: for every individual the most probable haplotype pair under the\n"
     "                        final model, found exactly (no k-best cut), with its status and posterior\n"
-    "  --extended-range      the six options above in extended range: individuals whose likelihood\n"
+    "  --output-ranked FILE [--ranked K]  write FILE: for every individual the K most probable haplotype\n"
+    "                        pairs under the final model, each once, in order, with their posteriors\n"
+    "                        (default K = 4, at most 16; an exact ranking, no k-best cut)\n"
+    "  --extended-range      the seven options above in extended range: individuals whose likelihood\n"
     "                        underflows a double (panels of more than about 1 200 loci) get lines too";
 
 // 0 on success; otherwise `err` says what is wrong (a missing value, an
@@ -98,6 +104,8 @@ inline int parse_options(int argc, const char *const *argv, Options &o, std::str
     else if (a == "--draws") { if (!next()) return 1; o.draws = atoi(v); o.have_draws = true; }
     else if (a == "--output-dosages") { if (!next()) return 1; o.output_dosages = v; }
     else if (a == "--output-map") { if (!next()) return 1; o.output_map = v; }
+    else if (a == "--output-ranked") { if (!next()) return 1; o.output_ranked = v; }
+    else if (a == "--ranked") { if (!next()) return 1; o.ranked = atoi(v); o.have_ranked = true; }
     else if (a == "--haplotypes") { if (!next()) return 1; o.haplotypes = v; }
     else if (a == "--extended-range") o.extended_range = true;
     else if (a == "--seed") { if (!next()) return 1; o.seed = strtoull(v, nullptr, 10); o.have_seed = true; }
@@ -131,9 +139,17 @@ inline int parse_options(int argc, const char *const *argv, Options &o, std::str
     err = "--output-dosages FILE and --haplotypes HAPFILE need each other\n" + std::string(USAGE);
     return 1;
   }
+  if (!o.output_ranked.empty() && (o.ranked < 1 || o.ranked > 16)) {
+    err = "--output-ranked needs --ranked K with 1 <= K <= 16\n" + std::string(USAGE);
+    return 1;
+  }
+  if (o.have_ranked && o.output_ranked.empty()) {
+    err = "--ranked needs --output-ranked FILE\n" + std::string(USAGE);
+    return 1;
+  }
   if (o.extended_range && !o.output_posteriors && !o.output_switch_posteriors && o.output_pair_posteriors.empty() &&
-      o.output_draws.empty() && o.output_dosages.empty() && o.output_map.empty()) {
-    err = "--extended-range needs --output-posteriors, --output-switch-posteriors, --output-pair-posteriors, --output-draws, --output-dosages or --output-map\n" +
+      o.output_draws.empty() && o.output_dosages.empty() && o.output_map.empty() && o.output_ranked.empty()) {
+    err = "--extended-range needs --output-posteriors, --output-switch-posteriors, --output-pair-posteriors, --output-draws, --output-dosages, --output-map or --output-ranked\n" +
           std::string(USAGE);
     return 1;
   }

@@ -13,8 +13,8 @@
 //               [--output-patterns x] [--output-posteriors] [--output-switch-posteriors]
 //               [--output-pair-posteriors FILE --pair-span K]
 //               [--output-draws FILE [--draws 100] [--seed 0]]
-//               [--output-dosages FILE --haplotypes HAPFILE] [--output-map FILE] [--extended-range]
-//               [--device 0] datafile ...
+//               [--output-dosages FILE --haplotypes HAPFILE] [--output-map FILE]
+//               [--output-ranked FILE [--ranked 4]] [--extended-range] [--device 0] datafile ...
 // --output-posteriors (no reference counterpart) writes <first file>.posteriors:
 // genotype posteriors at the loci with a missing input allele, under the final
 // model (hmc_write_posteriors).  --output-switch-posteriors (none either)
@@ -32,7 +32,10 @@
 // --output-map FILE (none either) writes FILE: every individual's most
 // probable haplotype pair under the final model, found exactly, with its
 // status and posterior (hmc_write_map_phase).
-// --extended-range (none either) runs those six in extended range
+// --output-ranked FILE [--ranked K] (none either) writes FILE: every
+// individual's K most probable haplotype pairs under the final model, each
+// once, in order, with their posteriors (hmc_write_ranked_phasings).
+// --extended-range (none either) runs those seven in extended range
 // (hmc_set_posterior_range): individuals whose likelihood underflows a double
 // get lines too.
 #include <cstdio>
@@ -146,6 +149,9 @@ int main(int argc, char **argv) {
   }
   if (!o.output_map.empty()) {  // of the same E-step
     if ((rc = hmc_write_map_phase(ctx, o.output_map.c_str()))) die("hmc_write_map_phase");
+  }
+  if (!o.output_ranked.empty()) {  // of the same E-step
+    if ((rc = hmc_write_ranked_phasings(ctx, o.output_ranked.c_str(), o.ranked))) die("hmc_write_ranked_phasings");
   }
   hmc_ctx_destroy(ctx);
   return 0;
