@@ -136,6 +136,58 @@ struct SegScratch {
   uint32_t *smeta;
 };
 
+// The final window [first, last) of 2 or 3 elements (std::__insertion_sort,
+// stl_algo.h:1819-1849, comp = greater) as a placement: where each element of
+// the window ends up, from the three comparisons the sequential code can make.
+// With a, b, c the values at first, first + 1, first + 2 and s = b > a,
+// ca = c > a, cb = c > b (ca = cb = false in a window of 2):
+//   i = 1: b goes before a iff s; call the pair (p, q) = s ? (b, a) : (a, b).
+//   i = 2: c goes to the front iff c > p (cp = s ? cb : ca); else
+//          __unguarded_linear_insert passes q iff c > q and then stops at p
+//          (c > p is known false), so c passes q iff t = ca || cb.
+// End offsets:  c: 2 - cp - t    p: cp    q: 1 + t, i.e.
+//   a: s ? 1 + t : ca        b: s ? cb : 1 + t        c: 2 - cp - t
+// On a weak ordering this is the stable descending rank, offset(x_j) =
+// #{i : x_i > x_j} + #{i < j : x_i equivalent to x_j} (s && cb implies ca, and
+// so on); the case form above is also what the sequential code does on values
+// that are no weak ordering (NaN compares false both ways), which the rank
+// count is not.  The offsets of all eight outcomes are packed two bits each
+// into one 48-bit constant (bits [16 j + 2 idx, +2): the element at window
+// offset j under idx = 4 s + 2 ca + cb), so a lane owns the element at its
+// position and gets that element's end offset with one shift; a window of 2 is
+// a window of 3 whose c is NaN (ca = cb = false).  A lane whose position is
+// outside a live window writes its element back to its own slot, so the writes
+// need no exec mask.  No swap network, no 3-way select, no branch.
+constexpr uint64_t small_window_table() {
+  uint64_t T = 0;
+  for (int idx = 0; idx < 8; ++idx) {
+    const int s = (idx >> 2) & 1, ca = (idx >> 1) & 1, cb = idx & 1;
+    const int t = ca | cb, cp = s ? cb : ca;
+    const uint64_t a = s ? 1 + t : ca, b = s ? cb : 1 + t, c = 2 - cp - t;
+    T |= a << (2 * idx) | b << (16 + 2 * idx) | c << (32 + 2 * idx);
+  }
+  return T;
+}
+// (a, b, c) end offsets for idx = 0 .. 7, written out from the sequential code:
+// (0,1,2) (0,2,1) (1,2,0) (1,2,0) (1,0,2) (2,1,0) (2,0,1) (2,1,0)
+// (tests/test_small_window_rank.py holds the same constant)
+static_assert(small_window_table() == 0x120644a9a950ull, "small-window placement table");
+struct SmallWindow {
+  int idx2;  // 2 * (4 s + 2 ca + cb)
+  int len;   // 2 or 3; 0 where the segment does not run the sort
+  __device__ SmallWindow(double a, double b, double c, int len_, bool live) : len(live ? len_ : 0) {
+    const double c3 = len_ > 2 ? c : __builtin_nan("");
+    idx2 = (b > a ? 8 : 0) | (c3 > a ? 4 : 0) | (c3 > b ? 2 : 0);
+  }
+  // destination of the element at position p
+  __device__ int dest(int p, int first) const {
+    constexpr uint64_t T = small_window_table();
+    const int j = p - first;
+    const int off = (int)(uint32_t)(T >> ((idx2 + 16 * j) & 63)) & 3;
+    return (unsigned)j < (unsigned)len ? first + off : p;
+  }
+};
+
 // std::nth_element(v, v+nth, v+n, greater) on every segment's list, in
 // place in the LDS slots slik/smeta (segment g's element k in slot
 // g*SW + k; n, nth uniform inside a segment, n <= SW <= 64; n == 0 marks an
@@ -243,35 +295,19 @@ __device__ inline void seg_nth_slots(int n, int nth, const Seg &sg, const SegScr
     wave_lds_sync();
   }
   // std::__insertion_sort of the <= 3 remaining elements (stl_algo.h:1819-1849)
+  // as a rank placement (header comment): reads, then writes, then visible
   const bool ins = act && !heap && last - first > 1;
   if (wave_ballot(ins)) {
-    const int len = last - first;
     const int f0 = first < kmax ? first : kmax;
     const int f1 = first + 1 < kmax ? first + 1 : kmax, f2 = first + 2 < kmax ? first + 2 : kmax;
-    double x0 = sl[f0], x1 = sl[f1], x2 = sl[f2];
-    uint32_t y0 = sm[f0], y1 = sm[f1], y2 = sm[f2];
-    if (x1 > x0) {
-      const double t = x1; x1 = x0; x0 = t;
-      const uint32_t u = y1; y1 = y0; y0 = u;
-    }
-    if (len > 2) {
-      if (x2 > x0) {
-        const double t = x2; const uint32_t u = y2;
-        x2 = x1; y2 = y1; x1 = x0; y1 = y0; x0 = t; y0 = u;
-      } else if (x2 > x1) {
-        const double t = x2; const uint32_t u = y2;
-        x2 = x1; y2 = y1; x1 = t; y1 = u;
-      }
-    }
-    const int j = k - first;
-    const bool mine = ins && (j == 0 || j == 1 || (j == 2 && len > 2));
-    const double xv = j == 0 ? x0 : (j == 1 ? x1 : x2);
-    const uint32_t yv = j == 0 ? y0 : (j == 1 ? y1 : y2);
+    const double y0 = sl[f0], y1 = sl[f1], y2 = sl[f2];
+    const double v = sl[k];
+    const uint32_t m = sm[k];
+    const SmallWindow sw3(y0, y1, y2, last - first, ins);
+    const int d = sw3.dest(k, first);
     wave_lds_sync();
-    if (mine) {
-      ss.slik[lane] = xv;
-      ss.smeta[lane] = yv;
-    }
+    sl[d] = v;
+    sm[d] = m;
     wave_lds_sync();
   }
 }
@@ -371,40 +407,21 @@ __device__ inline void seg2_nth_slots(int n, int nth, const Seg &sg, const SegSc
     wave_lds_sync();
   }
   // std::__insertion_sort of the <= 3 remaining elements (stl_algo.h:1819-1849)
+  // as a rank placement (header comment): reads, then writes, then visible
   const bool ins = act && !heap && last - first > 1;
   if (wave_ballot(ins)) {
-    const int len = last - first;
     const int f0 = first < kmax ? first : kmax;
     const int f1 = first + 1 < kmax ? first + 1 : kmax, f2 = first + 2 < kmax ? first + 2 : kmax;
-    double y0 = sl[f0], y1 = sl[f1], y2 = sl[f2];
-    uint32_t t0 = sm[f0], t1 = sm[f1], t2 = sm[f2];
-    if (y1 > y0) {
-      const double t = y1; y1 = y0; y0 = t;
-      const uint32_t u = t1; t1 = t0; t0 = u;
-    }
-    if (len > 2) {
-      if (y2 > y0) {
-        const double t = y2; const uint32_t u = t2;
-        y2 = y1; t2 = t1; y1 = y0; t1 = t0; y0 = t; t0 = u;
-      } else if (y2 > y1) {
-        const double t = y2; const uint32_t u = t2;
-        y2 = y1; t2 = t1; y1 = t; t1 = u;
-      }
-    }
-    const int j0 = p0 - first, j1 = p1 - first;
-    const bool mine0 = ins && (j0 == 0 || j0 == 1 || (j0 == 2 && len > 2));
-    const bool mine1 = ins && (j1 == 0 || j1 == 1 || (j1 == 2 && len > 2));
-    const double z0 = j0 == 0 ? y0 : (j0 == 1 ? y1 : y2), z1 = j1 == 0 ? y0 : (j1 == 1 ? y1 : y2);
-    const uint32_t u0 = j0 == 0 ? t0 : (j0 == 1 ? t1 : t2), u1 = j1 == 0 ? t0 : (j1 == 1 ? t1 : t2);
+    const double y0 = sl[f0], y1 = sl[f1], y2 = sl[f2];
+    const double v0 = sl[p0], v1 = sl[p1];
+    const uint32_t m0 = sm[p0], m1 = sm[p1];
+    const SmallWindow sw3(y0, y1, y2, last - first, ins);
+    const int d0 = sw3.dest(p0, first), d1 = sw3.dest(p1, first);
     wave_lds_sync();
-    if (mine0) {
-      sl[p0] = z0;
-      sm[p0] = u0;
-    }
-    if (mine1) {
-      sl[p1] = z1;
-      sm[p1] = u1;
-    }
+    sl[d0] = v0;
+    sm[d0] = m0;
+    sl[d1] = v1;
+    sm[d1] = m1;
     wave_lds_sync();
   }
 }

@@ -1704,7 +1704,10 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(WPE))) voi
         if (r0 == ce) {  // the list is final: zero the unused link words
           for (int q = k; q < S; ++q) tl[q] = 0u;
         }
-        tr.hdr[t] = (hd & 0xFFFFu) | (uint32_t)k << 16;
+        // (a chain's state: its list ends with S links, whatever the adds bring;
+        // nothing reads the record's count before the chain's end, which
+        // therefore need not load the header word again to rewrite it)
+        tr.hdr[t] = (hd & 0xFFFFu) | (uint32_t)(r0 == ce ? k : S) << 16;
         *Y.fwd(t) = fwd;
         *Y.hm(t) = yhm;  // (a chain's state: the flags of its partial list; the chain's end rewrites them)
         *Y.nl(t) = (uint32_t)k;
@@ -1845,10 +1848,9 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(WPE))) voi
                 Y.lik(st)[sg.k] = *slot_l;
                 tl[sg.k] = *slot_m;
               }
-              if (sg.k == 0) {
+              if (sg.k == 0) {  // (the record's header word has held the count S since phase A)
                 *Y.nl(st) = (uint32_t)S;
                 *Y.hm(st) = hb;
-                tr.hdr[st] = (Rhd[st] & 0xFFFFu) | (uint32_t)S << 16;
               }
               ci = -1;
             }
