@@ -894,15 +894,28 @@ int hmc_genotype_posteriors(hmc_ctx *h, int64_t *n_sites, int *n_pairs, int32_t 
   return HMC_OK;
 }
 
+// hmc_last_*_stats: the kind's record of its last call (Ctx::QueryStats) into the outputs its getter has
+static int query_stats(const hmc_ctx *h, Ctx::XpMode kind, double *structure_ms, double *fb_ms, double *sweep_ms, int *groups,
+                       int *n_pruned = nullptr, int *n_spilled = nullptr, int *slots = nullptr, int *rounds = nullptr,
+                       int *built = nullptr, int *batches = nullptr) {
+  if (!h) return HMC_EARG;
+  const Ctx::QueryStats &s = h->c.qstats[kind];
+  if (structure_ms) *structure_ms = s.ms_struct;
+  if (fb_ms) *fb_ms = s.ms_fb;
+  if (sweep_ms) *sweep_ms = s.ms_sweep;
+  if (groups) *groups = s.groups;
+  if (n_pruned) *n_pruned = s.pruned;
+  if (n_spilled) *n_spilled = s.spilled;
+  if (slots) *slots = s.slots;
+  if (rounds) *rounds = s.rounds;
+  if (built) *built = s.built;
+  if (batches) *batches = s.batches;
+  return HMC_OK;
+}
+
 int hmc_last_posterior_stats(const hmc_ctx *h, double *structure_ms, double *fb_ms, double *sites_ms, int *groups,
                              int *n_pruned) {
-  if (!h) return HMC_EARG;
-  if (structure_ms) *structure_ms = h->c.xp_ms_struct;
-  if (fb_ms) *fb_ms = h->c.xp_ms_fb;
-  if (sites_ms) *sites_ms = h->c.xp_ms_sites;
-  if (groups) *groups = h->c.xp_groups;
-  if (n_pruned) *n_pruned = h->c.xp_pruned;
-  return HMC_OK;
+  return query_stats(h, Ctx::XP_GENOTYPE, structure_ms, fb_ms, sites_ms, groups, n_pruned);
 }
 
 int hmc_switch_posteriors(hmc_ctx *h, int64_t *n_sites, int32_t *indiv, int32_t *locus_a, int32_t *locus_b, int32_t *status,
@@ -924,14 +937,7 @@ int hmc_switch_posteriors(hmc_ctx *h, int64_t *n_sites, int32_t *indiv, int32_t 
 
 int hmc_last_switch_stats(const hmc_ctx *h, double *structure_ms, double *fb_ms, double *sweep_ms, int *groups, int *n_pruned,
                           int *n_spilled) {
-  if (!h) return HMC_EARG;
-  if (structure_ms) *structure_ms = h->c.sw_ms_struct;
-  if (fb_ms) *fb_ms = h->c.sw_ms_fb;
-  if (sweep_ms) *sweep_ms = h->c.sw_ms_sweep;
-  if (groups) *groups = h->c.sw_groups;
-  if (n_pruned) *n_pruned = h->c.sw_pruned;
-  if (n_spilled) *n_spilled = h->c.sw_spilled;
-  return HMC_OK;
+  return query_stats(h, Ctx::XP_SWITCH, structure_ms, fb_ms, sweep_ms, groups, n_pruned, n_spilled);
 }
 
 int hmc_set_switch_tier(hmc_ctx *h, int states) {
@@ -964,16 +970,7 @@ int hmc_pair_span_list(hmc_ctx *h, int span, int64_t *n, int32_t *indiv, int32_t
 
 int hmc_last_pair_stats(const hmc_ctx *h, double *structure_ms, double *fb_ms, double *sweep_ms, int *groups, int *n_pruned,
                         int *n_spilled, int *slots, int *max_rounds) {
-  if (!h) return HMC_EARG;
-  if (structure_ms) *structure_ms = h->c.pr_ms_struct;
-  if (fb_ms) *fb_ms = h->c.pr_ms_fb;
-  if (sweep_ms) *sweep_ms = h->c.pr_ms_sweep;
-  if (groups) *groups = h->c.pr_groups;
-  if (n_pruned) *n_pruned = h->c.pr_pruned;
-  if (n_spilled) *n_spilled = h->c.pr_spilled;
-  if (slots) *slots = h->c.pr_ns;
-  if (max_rounds) *max_rounds = h->c.pr_rounds;
-  return HMC_OK;
+  return query_stats(h, Ctx::XP_PAIR, structure_ms, fb_ms, sweep_ms, groups, n_pruned, n_spilled, slots, max_rounds);
 }
 
 int hmc_set_pair_tuning(hmc_ctx *h, int slots, int tier_states) {
@@ -998,16 +995,7 @@ int hmc_haplotype_dosages(hmc_ctx *h, int64_t n, const int32_t *indiv, int n_pat
 
 int hmc_last_dosage_stats(const hmc_ctx *h, double *structure_ms, double *fb_ms, double *sweep_ms, int *groups, int *n_pruned,
                           int *n_spilled, int *slots, int *rounds) {
-  if (!h) return HMC_EARG;
-  if (structure_ms) *structure_ms = h->c.ds_ms_struct;
-  if (fb_ms) *fb_ms = h->c.ds_ms_fb;
-  if (sweep_ms) *sweep_ms = h->c.ds_ms_sweep;
-  if (groups) *groups = h->c.ds_groups;
-  if (n_pruned) *n_pruned = h->c.ds_pruned;
-  if (n_spilled) *n_spilled = h->c.ds_spilled;
-  if (slots) *slots = h->c.ds_ns;
-  if (rounds) *rounds = h->c.ds_rounds;
-  return HMC_OK;
+  return query_stats(h, Ctx::XP_DOSE, structure_ms, fb_ms, sweep_ms, groups, n_pruned, n_spilled, slots, rounds);
 }
 
 int hmc_set_dosage_tuning(hmc_ctx *h, int slots, int tier_states) {
@@ -1045,21 +1033,11 @@ int hmc_genotype_likelihoods(hmc_ctx *h, int64_t n, const int32_t *indiv, double
 }
 
 int hmc_last_likelihood_stats(const hmc_ctx *h, double *structure_ms, double *fb_ms, int *groups) {
-  if (!h) return HMC_EARG;
-  if (structure_ms) *structure_ms = h->c.lk_ms_struct;
-  if (fb_ms) *fb_ms = h->c.lk_ms_fb;
-  if (groups) *groups = h->c.lk_groups;
-  return HMC_OK;
+  return query_stats(h, Ctx::XP_LIK, structure_ms, fb_ms, nullptr, groups);
 }
 
 int hmc_last_draw_stats(const hmc_ctx *h, double *structure_ms, double *fb_ms, double *draw_ms, int *groups, int *n_pruned) {
-  if (!h) return HMC_EARG;
-  if (structure_ms) *structure_ms = h->c.dr_ms_struct;
-  if (fb_ms) *fb_ms = h->c.dr_ms_fb;
-  if (draw_ms) *draw_ms = h->c.dr_ms_draw;
-  if (groups) *groups = h->c.dr_groups;
-  if (n_pruned) *n_pruned = h->c.dr_pruned;
-  return HMC_OK;
+  return query_stats(h, Ctx::XP_DRAW, structure_ms, fb_ms, draw_ms, groups, n_pruned);
 }
 
 int hmc_map_phase(hmc_ctx *h, int64_t n, const int32_t *indiv, int32_t *hap, double *prob, int32_t *status) {
@@ -1070,13 +1048,7 @@ int hmc_map_phase(hmc_ctx *h, int64_t n, const int32_t *indiv, int32_t *hap, dou
 }
 
 int hmc_last_map_stats(const hmc_ctx *h, double *structure_ms, double *fb_ms, double *sweep_ms, int *groups, int *n_pruned) {
-  if (!h) return HMC_EARG;
-  if (structure_ms) *structure_ms = h->c.mp_ms_struct;
-  if (fb_ms) *fb_ms = h->c.mp_ms_fb;
-  if (sweep_ms) *sweep_ms = h->c.mp_ms_sweep;
-  if (groups) *groups = h->c.mp_groups;
-  if (n_pruned) *n_pruned = h->c.mp_pruned;
-  return HMC_OK;
+  return query_stats(h, Ctx::XP_MAP, structure_ms, fb_ms, sweep_ms, groups, n_pruned);
 }
 
 int hmc_ranked_phasings(hmc_ctx *h, int64_t n, const int32_t *indiv, int k, int32_t *hap, double *prob, int32_t *count,
@@ -1089,14 +1061,7 @@ int hmc_ranked_phasings(hmc_ctx *h, int64_t n, const int32_t *indiv, int k, int3
 
 int hmc_last_ranked_stats(const hmc_ctx *h, double *structure_ms, double *fb_ms, double *sweep_ms, int *groups, int *n_pruned,
                           int *k_built) {
-  if (!h) return HMC_EARG;
-  if (structure_ms) *structure_ms = h->c.rk_ms_struct;
-  if (fb_ms) *fb_ms = h->c.rk_ms_fb;
-  if (sweep_ms) *sweep_ms = h->c.rk_ms_sweep;
-  if (groups) *groups = h->c.rk_groups;
-  if (n_pruned) *n_pruned = h->c.rk_pruned;
-  if (k_built) *k_built = h->c.rk_built;
-  return HMC_OK;
+  return query_stats(h, Ctx::XP_RANK, structure_ms, fb_ms, sweep_ms, groups, n_pruned, nullptr, nullptr, nullptr, k_built);
 }
 
 // Test seam of hmc_ranked_phasings (not in the public header; results do not
@@ -1110,9 +1075,7 @@ int hmc_set_ranked_tuning(hmc_ctx *h, uint64_t store_bytes) {
 }
 
 int hmc_last_ranked_batches(const hmc_ctx *h, int *batches) {
-  if (!h) return HMC_EARG;
-  if (batches) *batches = h->c.rk_batches;
-  return HMC_OK;
+  return query_stats(h, Ctx::XP_RANK, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, batches);
 }
 
 // Test seam of hmc_posterior_draws (not in the public header; results do not
@@ -1308,182 +1271,132 @@ int hmc_write_pair_posteriors(hmc_ctx *h, const char *path, int span) {
   return HMC_OK;
 }
 
-int hmc_write_haplotype_dosages(hmc_ctx *h, const char *path, int n_patterns, const char *const *names, const int32_t *start,
-                                const int32_t *len, int maxlen, const int32_t *alleles_a, const int32_t *alleles_b) {
-  if (!h || !path || !h->c.have_panel) return HMC_EARG;
-  Ctx &c = h->c;
-  if (n_patterns < 0 || (n_patterns > 0 && !names)) return c.fail(HMC_EARG, "haplotype dosages: no pattern names given");
-  const int n = c.nloc(), P = n_patterns;
-  // individuals in batches whose rows take at most 64 MiB of host memory; a row does not depend on the
-  // other individuals of its call, so the lines are those of one call for the shard
-  const int nb = (int)std::max<size_t>(1, std::min<size_t>((size_t)std::max(n, 1), ((size_t)8 << 20) / (size_t)std::max(P, 1)));
-  std::vector<int32_t> status(nb), indiv(nb);
-  std::vector<double> dose((size_t)nb * P);
+// The per-individual writers: the shard through `query` in batches of nb individuals, each individual's lines by
+// `lines(fp, i, id)` (i: its position in the batch).  A result does not depend on the other individuals of its
+// call, so the lines are those of one call for the shard.
+static int write_batches(Ctx &c, const char *path, int nb, const char *header, const std::function<int(int, const int32_t *)> &query,
+                         const std::function<void(FILE *, int, const char *)> &lines) {
+  const int n = c.nloc();
+  std::vector<int32_t> indiv(nb);
   FILE *fp = nullptr;
   hmc::FileData d;
   for (int b0 = 0; b0 < n || !fp; b0 += nb) {
     const int k = std::max(0, std::min(nb, n - b0));
     for (int i = 0; i < k; ++i) indiv[i] = c.i0 + b0 + i;
-    int rc;
     // (the first batch before the file is opened: a call that fails leaves no file behind)
-    if ((rc = c.haplotype_dosages(k, indiv.data(), P, start, len, maxlen, alleles_a, alleles_b, dose.data(), status.data()))) {
+    if (int rc = query(k, indiv.data())) {
       if (fp) fclose(fp);
       return rc;
     }
     if (!fp) {
       if (!(fp = fopen(path, "w"))) return c.fail(HMC_EIO, "Can not open file %s!", path);
       d = writer_meta(c);
-      fprintf(fp, "Id\tHaplotype\tDosage\n");
+      fputs(header, fp);
     }
-    for (int i = 0; i < k; ++i) {
-      if (status[i] != 0 || P == 0) continue;
-      for (int p = 0; p < P; ++p) fprintf(fp, "%s\t%s\t%.17g\n", d.ids[indiv[i]].c_str(), names[p], dose[(size_t)i * P + p]);
-    }
+    for (int i = 0; i < k; ++i) lines(fp, i, d.ids[indiv[i]].c_str());
   }
   const bool bad = ferror(fp) != 0;
   if (fclose(fp) != 0 || bad) return c.fail(HMC_EIO, "Can not write file %s!", path);
   return HMC_OK;
+}
+
+// individuals per batch when one takes `per` entries and a batch at most `entries` of them
+static int batch_size(const Ctx &c, size_t entries, size_t per) {
+  return (int)std::max<size_t>(1, std::min<size_t>((size_t)std::max(c.nloc(), 1), entries / std::max<size_t>(per, 1)));
+}
+static constexpr size_t HAP_BATCH = (size_t)64 << 20;  // haplotype entries: at most 256 MiB of host memory
+
+// One haplotype as the genotype files spell alleles: characters ('S') or integers ('M'), '?' for a missing input
+// allele (MAP rows of status 1 or 2 only); lead: what stands before the first allele (0: nothing).
+static void spell_alleles(FILE *fp, const Ctx &c, const int32_t *row, char lead) {
+  for (int l = 0; l < c.pan.L; ++l) {
+    if (l) fputc(' ', fp);
+    else if (lead) fputc(lead, fp);
+    if (row[l] < 0) fputc('?', fp);
+    else if (c.pan.types[l] == 'S') fputc((char)row[l], fp);
+    else fprintf(fp, "%d", row[l]);
+  }
+}
+
+int hmc_write_haplotype_dosages(hmc_ctx *h, const char *path, int n_patterns, const char *const *names, const int32_t *start,
+                                const int32_t *len, int maxlen, const int32_t *alleles_a, const int32_t *alleles_b) {
+  if (!h || !path || !h->c.have_panel) return HMC_EARG;
+  Ctx &c = h->c;
+  if (n_patterns < 0 || (n_patterns > 0 && !names)) return c.fail(HMC_EARG, "haplotype dosages: no pattern names given");
+  const int P = n_patterns;
+  const int nb = batch_size(c, (size_t)8 << 20, (size_t)P);  // rows of at most 64 MiB of host memory
+  std::vector<int32_t> status(nb);
+  std::vector<double> dose((size_t)nb * P);
+  return write_batches(
+      c, path, nb, "Id\tHaplotype\tDosage\n",
+      [&](int k, const int32_t *indiv) {
+        return c.haplotype_dosages(k, indiv, P, start, len, maxlen, alleles_a, alleles_b, dose.data(), status.data());
+      },
+      [&](FILE *fp, int i, const char *id) {
+        for (int p = 0; status[i] == 0 && p < P; ++p) fprintf(fp, "%s\t%s\t%.17g\n", id, names[p], dose[(size_t)i * P + p]);
+      });
 }
 
 int hmc_write_posterior_draws(hmc_ctx *h, const char *path, int draws, uint64_t seed) {
   if (!h || !path || !h->c.have_panel) return HMC_EARG;
   Ctx &c = h->c;
   if (draws < 1) return c.fail(HMC_EARG, "posterior draws: draws = %d is below 1", draws);
-  const int n = c.nloc(), L = c.pan.L;
-  // individuals in batches whose haplotypes take at most 256 MiB of host memory; a draw does not
-  // depend on the other individuals of its call, so the lines are those of one call for the shard
+  const int L = c.pan.L;
   const size_t per = (size_t)draws * 2 * L;
-  const int nb = (int)std::max<size_t>(1, std::min<size_t>((size_t)std::max(n, 1), ((size_t)64 << 20) / per));
-  std::vector<int32_t> hap((size_t)nb * per), status(nb), indiv(nb);
+  const int nb = batch_size(c, HAP_BATCH, per);
+  std::vector<int32_t> hap((size_t)nb * per), status(nb);
   std::vector<double> prob((size_t)nb * draws);
-  FILE *fp = nullptr;
-  hmc::FileData d;
-  for (int b0 = 0; b0 < n || !fp; b0 += nb) {
-    const int k = std::max(0, std::min(nb, n - b0));
-    for (int i = 0; i < k; ++i) indiv[i] = c.i0 + b0 + i;
-    int rc;
-    // (the first batch before the file is opened: a call that fails leaves no file behind)
-    if ((rc = c.posterior_draws(k, indiv.data(), draws, seed, hap.data(), prob.data(), status.data()))) {
-      if (fp) fclose(fp);
-      return rc;
-    }
-    if (!fp) {
-      if (!(fp = fopen(path, "w"))) return c.fail(HMC_EIO, "Can not open file %s!", path);
-      d = writer_meta(c);
-      fprintf(fp, "Id\tDraw\tPosterior\tHaplotype0\tHaplotype1\n");
-    }
-    for (int i = 0; i < k; ++i) {
-      if (status[i] != 0) continue;
-      for (int q = 0; q < draws; ++q) {
-        fprintf(fp, "%s\t%d\t%.17g", d.ids[indiv[i]].c_str(), q, prob[(size_t)i * draws + q]);
-        for (int side = 0; side < 2; ++side) {
-          const int32_t *row = hap.data() + (((size_t)i * draws + q) * 2 + side) * L;
-          for (int l = 0; l < L; ++l) {  // as the genotype files spell alleles: characters ('S') or integers ('M')
-            fputc(l ? ' ' : '\t', fp);
-            if (c.pan.types[l] == 'S') fputc((char)row[l], fp);
-            else fprintf(fp, "%d", row[l]);
-          }
+  return write_batches(
+      c, path, nb, "Id\tDraw\tPosterior\tHaplotype0\tHaplotype1\n",
+      [&](int k, const int32_t *indiv) { return c.posterior_draws(k, indiv, draws, seed, hap.data(), prob.data(), status.data()); },
+      [&](FILE *fp, int i, const char *id) {
+        for (int q = 0; status[i] == 0 && q < draws; ++q) {
+          fprintf(fp, "%s\t%d\t%.17g", id, q, prob[(size_t)i * draws + q]);
+          for (int side = 0; side < 2; ++side) spell_alleles(fp, c, hap.data() + (((size_t)i * draws + q) * 2 + side) * L, '\t');
+          fputc('\n', fp);
         }
-        fputc('\n', fp);
-      }
-    }
-  }
-  const bool bad = ferror(fp) != 0;
-  if (fclose(fp) != 0 || bad) return c.fail(HMC_EIO, "Can not write file %s!", path);
-  return HMC_OK;
+      });
 }
 
 int hmc_write_map_phase(hmc_ctx *h, const char *path) {
   if (!h || !path || !h->c.have_panel) return HMC_EARG;
   Ctx &c = h->c;
-  const int n = c.nloc(), L = c.pan.L;
-  // individuals in batches whose haplotypes take at most 256 MiB of host memory, as hmc_write_posterior_draws:
-  // an individual's result does not depend on the others of its call
+  const int L = c.pan.L;
   const size_t per = (size_t)2 * L;
-  const int nb = (int)std::max<size_t>(1, std::min<size_t>((size_t)std::max(n, 1), ((size_t)64 << 20) / per));
-  std::vector<int32_t> hap((size_t)nb * per), status(nb), indiv(nb);
+  const int nb = batch_size(c, HAP_BATCH, per);
+  std::vector<int32_t> hap((size_t)nb * per), status(nb);
   std::vector<double> prob(nb);
-  FILE *fp = nullptr;
-  hmc::FileData d;
-  for (int b0 = 0; b0 < n || !fp; b0 += nb) {
-    const int k = std::max(0, std::min(nb, n - b0));
-    for (int i = 0; i < k; ++i) indiv[i] = c.i0 + b0 + i;
-    int rc;
-    // (the first batch before the file is opened: a call that fails leaves no file behind)
-    if ((rc = c.map_phase(k, indiv.data(), hap.data(), prob.data(), status.data()))) {
-      if (fp) fclose(fp);
-      return rc;
-    }
-    if (!fp) {
-      if (!(fp = fopen(path, "w"))) return c.fail(HMC_EIO, "Can not open file %s!", path);
-      d = writer_meta(c);
-      fprintf(fp, "Id\tStatus\tPosterior\n");
-    }
-    for (int i = 0; i < k; ++i) {
-      fprintf(fp, "%s\t%d\t%.17g\n", d.ids[indiv[i]].c_str(), status[i], prob[i]);
-      for (int side = 0; side < 2; ++side) {
-        const int32_t *row = hap.data() + ((size_t)i * 2 + side) * L;
-        for (int l = 0; l < L; ++l) {  // as the genotype files spell alleles: characters ('S') or integers ('M')
-          if (l) fputc(' ', fp);
-          if (row[l] < 0) fputc('?', fp);  // (a missing input allele in a row of status 1 or 2)
-          else if (c.pan.types[l] == 'S') fputc((char)row[l], fp);
-          else fprintf(fp, "%d", row[l]);
+  return write_batches(
+      c, path, nb, "Id\tStatus\tPosterior\n",
+      [&](int k, const int32_t *indiv) { return c.map_phase(k, indiv, hap.data(), prob.data(), status.data()); },
+      [&](FILE *fp, int i, const char *id) {
+        fprintf(fp, "%s\t%d\t%.17g\n", id, status[i], prob[i]);
+        for (int side = 0; side < 2; ++side) {
+          spell_alleles(fp, c, hap.data() + ((size_t)i * 2 + side) * L, 0);
+          fputc('\n', fp);
         }
-        fputc('\n', fp);
-      }
-    }
-  }
-  const bool bad = ferror(fp) != 0;
-  if (fclose(fp) != 0 || bad) return c.fail(HMC_EIO, "Can not write file %s!", path);
-  return HMC_OK;
+      });
 }
 
 int hmc_write_ranked_phasings(hmc_ctx *h, const char *path, int k) {
   if (!h || !path || !h->c.have_panel) return HMC_EARG;
   Ctx &c = h->c;
   if (k < 1 || k > hmc::RANK_K_MAX) return c.fail(HMC_EARG, "ranked phasings: k = %d is outside [1, %d]", k, hmc::RANK_K_MAX);
-  const int n = c.nloc(), L = c.pan.L;
-  // individuals in batches whose haplotypes take at most 256 MiB of host memory, as hmc_write_posterior_draws:
-  // an individual's result does not depend on the others of its call
+  const int L = c.pan.L;
   const size_t per = (size_t)2 * L * k;
-  const int nb = (int)std::max<size_t>(1, std::min<size_t>((size_t)std::max(n, 1), ((size_t)64 << 20) / per));
-  std::vector<int32_t> hap((size_t)nb * per), status(nb), count(nb), indiv(nb);
+  const int nb = batch_size(c, HAP_BATCH, per);
+  std::vector<int32_t> hap((size_t)nb * per), status(nb), count(nb);
   std::vector<double> prob((size_t)nb * k);
-  FILE *fp = nullptr;
-  hmc::FileData d;
-  for (int b0 = 0; b0 < n || !fp; b0 += nb) {
-    const int m = std::max(0, std::min(nb, n - b0));
-    for (int i = 0; i < m; ++i) indiv[i] = c.i0 + b0 + i;
-    int rc;
-    // (the first batch before the file is opened: a call that fails leaves no file behind)
-    if ((rc = c.ranked_phasings(m, indiv.data(), k, hap.data(), prob.data(), count.data(), status.data()))) {
-      if (fp) fclose(fp);
-      return rc;
-    }
-    if (!fp) {
-      if (!(fp = fopen(path, "w"))) return c.fail(HMC_EIO, "Can not open file %s!", path);
-      d = writer_meta(c);
-      fprintf(fp, "Id\tRank\tPosterior\tHaplotype0\tHaplotype1\n");
-    }
-    for (int i = 0; i < m; ++i) {
-      if (status[i] != 0) continue;
-      for (int r = 0; r < count[i]; ++r) {
-        fprintf(fp, "%s\t%d\t%.17g", d.ids[indiv[i]].c_str(), r, prob[(size_t)i * k + r]);
-        for (int side = 0; side < 2; ++side) {
-          const int32_t *row = hap.data() + (((size_t)i * k + r) * 2 + side) * L;
-          for (int l = 0; l < L; ++l) {  // as the genotype files spell alleles: characters ('S') or integers ('M')
-            fputc(l ? ' ' : '\t', fp);
-            if (c.pan.types[l] == 'S') fputc((char)row[l], fp);
-            else fprintf(fp, "%d", row[l]);
-          }
+  return write_batches(
+      c, path, nb, "Id\tRank\tPosterior\tHaplotype0\tHaplotype1\n",
+      [&](int m, const int32_t *indiv) { return c.ranked_phasings(m, indiv, k, hap.data(), prob.data(), count.data(), status.data()); },
+      [&](FILE *fp, int i, const char *id) {
+        for (int r = 0; status[i] == 0 && r < count[i]; ++r) {
+          fprintf(fp, "%s\t%d\t%.17g", id, r, prob[(size_t)i * k + r]);
+          for (int side = 0; side < 2; ++side) spell_alleles(fp, c, hap.data() + (((size_t)i * k + r) * 2 + side) * L, '\t');
+          fputc('\n', fp);
         }
-        fputc('\n', fp);
-      }
-    }
-  }
-  const bool bad = ferror(fp) != 0;
-  if (fclose(fp) != 0 || bad) return c.fail(HMC_EIO, "Can not write file %s!", path);
-  return HMC_OK;
+      });
 }
 
 int hmc_last_timings(const hmc_ctx *h, double *f, double *t, double *m) {

@@ -1,9 +1,10 @@
 // ctx.hpp — the host runtime's context (Ctx): device buffers, the panel,
 // the pattern table, the E-step stores and the EM state of one rank.  The
 // member functions live in ctx_panel.cpp (collectives, panel upload),
-// ctx_mine.cpp (pattern search), ctx_exact.cpp (exact M-step), ctx_estep.cpp
-// (E-step store planning and passes) and ctx_run.cpp (HaploComp, EM driver,
-// model snapshot); api.cpp holds the C-ABI.
+// ctx_mine.cpp (pattern search), ctx_exact.cpp (exact M-step), ctx_query.cpp
+// (the posterior queries on the exact lattice), ctx_estep.cpp (E-step store
+// planning and passes) and ctx_run.cpp (HaploComp, EM driver, model snapshot);
+// api.cpp holds the C-ABI.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>
@@ -27,6 +28,7 @@
 #include "haplofile.hpp"
 #include "hmc_internal.hpp"
 #include "mstep.hpp"
+#include "query_rows.hpp"
 #include "exact.hpp"
 #include "select.hpp"
 
@@ -811,6 +813,41 @@ struct Ctx {
   // what the exact group runs after exact_fb in place of the trie walk
   enum XpMode { XP_OFF = 0, XP_GENOTYPE = 1, XP_SWITCH = 2, XP_PAIR = 3, XP_DRAW = 4, XP_LIK = 5, XP_DOSE = 6, XP_MAP = 7, XP_RANK = 8 };
   XpMode xp_mode = XP_OFF;
+  // What the eight queries share (ctx_query.cpp).  Of a kind's last call:
+  // device ms of the structure passes, of exact_fb and of the kind's own
+  // kernels (draws_to_symbols included); groups; individuals on pruned
+  // records; individuals whose largest record exceeded the tier; the NS used;
+  // rounds (pairs: most of any individual, dosages: sweeps the plan takes); the
+  // list width KL of the ranked kernel that ran; launches.  A kind leaves at
+  // zero what it does not use.  The running pass writes its own kind's record.
+  struct QueryStats {
+    double ms_struct = 0, ms_fb = 0, ms_sweep = 0;
+    int groups = 0, pruned = 0, spilled = 0, slots = 0, rounds = 0, built = 0, batches = 0;
+  };
+  QueryStats qstats[XP_RANK + 1];  // by XpMode
+  // HMC_OK, or the error of a query that cannot run: no E-step yet, a model
+  // changed since it, more than 44 alleles per locus
+  int query_ready(XpMode kind);
+  // The running call's rows (draws, likelihoods, dosages, MAP, ranked): n < 0
+  // and entries outside the shard are HMC_EARG naming the entry.
+  QueryRows qr;
+  int query_rows(XpMode kind, int64_t n, const int32_t *indiv);
+  // `launch` between two events, then the stream drained: its device ms are the running kind's sweep time
+  int timed_sweep(const char *what, const std::function<int()> &launch);
+  // Frontiers past the tier (switch, pairs, dosages): the sweep's HBM scratch
+  // of 32 NS bytes per state and block, at most 1 GiB; may lower `grid`.
+  hipError_t spill_scratch(int NS, int fmax, int &grid, DevBuf<double> &buf);
+  // The per-individual queries (draws, MAP, ranked, dosages) over a group: its
+  // asked individuals in batches.  next(pos, nb): how many of sel[pos..) the
+  // next batch takes; run(xb, pos, nb): the kind's buffers, its timed launch,
+  // its results queued for the host; scatter(u, row, first): batch member u's
+  // result to a caller row (first: the individual's first row, written before
+  // the others and the stream drained in between).
+  std::vector<int32_t> asked_in(const int32_t *ids, int k) const;
+  int query_batches(const char *what, const ExactArgs &x, const std::vector<int32_t> &sel, DevBuf<int32_t> &d_ord,
+                    DevBuf<int32_t> &d_st, const std::function<int(size_t, int &)> &next,
+                    const std::function<int(const ExactArgs &, size_t, int)> &run,
+                    const std::function<hipError_t(int, int64_t, int64_t)> &scatter);
   // Extended range (hmc_set_posterior_range): the four posterior calls run
   // exact_fb's scaled pass (ExactArgs::extended) and divide by its own total,
   // so no individual is given up for underflow: no pruned re-run, no status 2.
@@ -825,9 +862,7 @@ struct Ctx {
     std::vector<double> mantissa;
     std::vector<int32_t> exponent, status;
   } lk;
-  double lk_ms_struct = 0, lk_ms_fb = 0;  // of the last call
-  int lk_groups = 0;
-  // The part the two posterior calls share: every individual of the shard
+  // The part every query shares: every individual of the shard
   // through estep_split(order, true) with xp_mode = mode, and whatever that
   // pass shares with the E-step saved before and put back after.
   // (only: the individuals of the shard that take part; the others are not touched)
@@ -846,9 +881,6 @@ struct Ctx {
   DevBuf<int32_t> d_sw_a, d_sw_b;
   DevBuf<double> d_sw_scratch;
   int sw_tier = 0;  // hmc_set_switch_tier (0: SWITCH_TIER_DEFAULT)
-  // of the last call, as xp_* below; sw_spilled: individuals whose largest record exceeded the tier
-  double sw_ms_struct = 0, sw_ms_fb = 0, sw_ms_sweep = 0;
-  int sw_groups = 0, sw_pruned = 0, sw_spilled = 0;
   size_t n_switch_last = 0;
   // Pair posteriors (hmc_pair_posteriors): caller-given queries (individual,
   // locus a < locus b, both heterozygous in the input), any distance apart;
@@ -874,11 +906,7 @@ struct Ctx {
   DevBuf<unsigned long long> d_pr_evoff;
   DevBuf<PairEvent> d_pr_ev;
   DevBuf<double> d_pr_scratch;
-  int pr_slots = 0, pr_tier = 0;  // hmc_set_pair_tuning (0: automatic)
-  int pr_ns_run = 0;              // NS of the running call
-  // of the last call, as sw_* above; pr_ns: the NS used, pr_rounds: most rounds of any individual
-  double pr_ms_struct = 0, pr_ms_fb = 0, pr_ms_sweep = 0;
-  int pr_groups = 0, pr_pruned = 0, pr_spilled = 0, pr_ns = 0, pr_rounds = 0;
+  int pr_slots = 0, pr_tier = 0;  // hmc_set_pair_tuning (0: automatic); the running call's NS: its record's slots
   // Haplotype dosages (hmc_haplotype_dosages): expected copies of caller-given
   // patterns (window, allele rows A and B) per asked individual;
   // exact_haplotype_dosages per group (XP_DOSE), in batches whose device
@@ -892,18 +920,12 @@ struct Ctx {
   struct DoseCall {  // the running call
     int P = 0, maxlen = 0, n_events = 0;
     double *dosage = nullptr;
-    std::vector<int64_t> row_off, rows;  // CSR over the shard's individuals: the caller's rows that ask for each
-    std::vector<int32_t> status;         // [shard] 1 until the individual's group has run
   } ds;
   DevBuf<DoseEvent> d_ds_ev;
   DevBuf<uint8_t> d_ds_codes;
   DevBuf<double> d_ds_out, d_ds_scratch;
   DevBuf<int32_t> d_ds_order, d_ds_status;
-  int ds_slots = 0, ds_tier = 0;  // hmc_set_dosage_tuning (0: automatic)
-  int ds_ns_run = 0;              // NS of the running call
-  // of the last call, as pr_* above; ds_rounds: sweeps over the records the plan takes
-  double ds_ms_struct = 0, ds_ms_fb = 0, ds_ms_sweep = 0;
-  int ds_groups = 0, ds_pruned = 0, ds_spilled = 0, ds_ns = 0, ds_rounds = 0;
+  int ds_slots = 0, ds_tier = 0;  // hmc_set_dosage_tuning (0: automatic); the running call's NS: its record's slots
   // Posterior draws (hmc_posterior_draws): `draws` haplotype pairs per asked
   // individual, sampled backwards through exact_fb's forward values;
   // exact_posterior_draws per group (XP_DRAW), in batches whose device output
@@ -917,9 +939,17 @@ struct Ctx {
     uint64_t seed = 0;
     int32_t *hap = nullptr;
     double *prob = nullptr;
-    std::vector<int64_t> row_off, rows;  // CSR over the shard's individuals: the caller's rows that ask for each
-    std::vector<int32_t> status;         // [shard] 1 until the individual's group has run
+    std::vector<int32_t> count;  // [shard] rows found (ranked phasings; else `draws`)
   } dr;
+  // What draws, MAP phasing (draws = 1) and ranked phasings (draws = k, count
+  // given) share: the rows, the pass of `kind`, and for rows past an
+  // individual's count (all of them when it ends unresolved) the input genotype.
+  int hap_query(XpMode kind, int64_t n, const int32_t *indiv, int draws, uint64_t seed, int32_t *hap, double *prob,
+                int32_t *count, int32_t *status);
+  // rows [from, rows) of caller entry q: the input genotype of shard individual i at probability 0
+  void input_genotype_rows(int64_t q, int i, int from, int rows, int32_t *hap, double *prob) const;
+  // the panel's symbol table, [locus][allele index], for draws_to_symbols: once per call
+  int upload_symtab(const char *what);
   DevBuf<int32_t> d_dr_order, d_dr_status, d_dr_hap, d_dr_sym;  // (hap, sym: the transposing kernel's)
   DevBuf<uint8_t> d_dr_al;
   DevBuf<double> d_dr_prob, d_dr_csum;
@@ -929,9 +959,6 @@ struct Ctx {
   // exact_fb skips its backward half
   int dr_lds_chunks = -1;
   bool dr_forward_only = true;  // exact_fb without its backward half for this call (hmc_set_draw_tuning)
-  // of the last call, as sw_* above; dr_ms_draw: exact_posterior_draws and draws_to_symbols
-  double dr_ms_struct = 0, dr_ms_fb = 0, dr_ms_draw = 0;
-  int dr_groups = 0, dr_pruned = 0;
   // MAP phasing (hmc_map_phase): the most probable haplotype pair per asked
   // individual and its exact posterior; exact_map_phase per group (XP_MAP)
   // after exact_fb's forward-only pass, whose x-store slots the sweep
@@ -940,10 +967,6 @@ struct Ctx {
   // Rows are the caller's, batches and device buffers the draws' with one draw.
   int map_phase(int64_t n, const int32_t *indiv, int32_t *hap, double *prob, int32_t *status);
   int map_group(const ExactArgs &x, const int32_t *ids, int k, int dev_cu);
-  DrawCall mp;  // the running call (draws = 1)
-  // of the last call, as dr_* above; mp_ms_sweep: exact_map_phase and draws_to_symbols
-  double mp_ms_struct = 0, mp_ms_fb = 0, mp_ms_sweep = 0;
-  int mp_groups = 0, mp_pruned = 0;
   // Ranked phasings (hmc_ranked_phasings): the k most probable haplotype
   // pairs per asked individual, each once, with their exact posteriors;
   // exact_ranked_phasings per group (XP_RANK) after exact_fb's forward-only
@@ -956,23 +979,14 @@ struct Ctx {
   // Rows are the caller's, output buffers the draws' with k draws.
   int ranked_phasings(int64_t n, const int32_t *indiv, int k, int32_t *hap, double *prob, int32_t *count, int32_t *status);
   int ranked_group(const ExactArgs &x, const int32_t *ids, int k, int dev_cu);
-  DrawCall rk;                     // the running call (draws = k)
-  std::vector<int32_t> rk_count;   // [shard] rows found
   DevBuf<uint8_t> d_rk_store;
   DevBuf<unsigned long long> d_rk_base, d_rk_total;
   DevBuf<int32_t> d_rk_count;
   uint64_t rk_store_bytes = 0;     // hmc_set_ranked_tuning (test seam): the list store's budget, 0 = the value store's
   uint64_t rank_budget_bytes() const { return rk_store_bytes ? rk_store_bytes : trace_budget * 4; }
-  // of the last call, as mp_* above; rk_built: the list width KL of the kernel that ran; rk_batches: launches
-  double rk_ms_struct = 0, rk_ms_fb = 0, rk_ms_sweep = 0;
-  int rk_groups = 0, rk_pruned = 0, rk_built = 0, rk_batches = 0;
   DevBuf<unsigned long long> d_site_off;
   DevBuf<int32_t> d_site_locus, d_site_status;
   DevBuf<double> d_site_post;
-  // of the last call: device ms of the structure passes, exact_fb and the site
-  // kernel, groups, individuals on pruned records
-  double xp_ms_struct = 0, xp_ms_fb = 0, xp_ms_sites = 0;
-  int xp_groups = 0, xp_pruned = 0;
   size_t n_sites_last = 0;
   // The trie walk of one group (the current round's trie).
   int exact_walk_group(ExactArgs &x, int k, int dev_cu);

@@ -1,4 +1,4 @@
-// ctx_exact.cpp — Ctx members: the exact M-step (--exact-estimate): PatternManager::estimatePatterns.
+// ctx_exact.cpp — Ctx members: the exact M-step (--exact-estimate): PatternManager::estimatePatterns (queries: ctx_query.cpp).
 #include "ctx.hpp"
 
 namespace hmc {
@@ -223,7 +223,7 @@ int Ctx::exact_group(const int32_t *ids, int k, const std::function<int(std::vec
     return hipfail(e, "exact_fb");
   auto fb_timed = [&]() {  // (posteriors only; the stream is drained at both call sites)
     float ms = 0;
-    if (xp_mode && hipEventElapsedTime(&ms, ev[0], ev[1]) == hipSuccess) xp_ms_fb += ms;
+    if (xp_mode && hipEventElapsedTime(&ms, ev[0], ev[1]) == hipSuccess) qstats[xp_mode].ms_fb += ms;
   };
   fb_timed();
   std::vector<int32_t> redo;
@@ -281,1113 +281,6 @@ int Ctx::exact_group(const int32_t *ids, int k, const std::function<int(std::vec
     return HMC_OK;
   }
   return exact_walk_group(x, k, dev_cu);
-}
-
-int Ctx::switch_group(const ExactArgs &x, const int32_t *ids, const std::vector<int32_t> &fm, int k, int dev_cu) {
-  SwitchArgs s;
-  s.site_off = d_site_off.p;
-  s.locus_a = d_sw_a.p;
-  s.locus_b = d_sw_b.p;
-  s.post = d_site_post.p;
-  s.site_status = d_site_status.p;
-  s.tier = sw_tier > 0 ? sw_tier : SWITCH_TIER_DEFAULT;
-  int grid = std::max(1, std::min(k, dev_cu * 8));
-  hipError_t e;
-  int spilled = 0;
-  for (int q = 0; q < k; ++q) spilled += fm[ids[q]] > s.tier;
-  sw_spilled += spilled;
-  if (spilled) {  // frontiers past the tier: 32 B per state and block in HBM, at most 1 GiB (the grid does not change the bits)
-    grid = (int)std::max<size_t>(1, std::min<size_t>((size_t)grid, ((size_t)1 << 30) / ((size_t)32 * x.fmax)));
-    if ((e = d_sw_scratch.ensure((size_t)grid * 4 * x.fmax))) return hipfail(e, "exact_switch_posteriors");
-    s.scratch = d_sw_scratch.p;
-    s.scratch_states = x.fmax;
-  }
-  hipEventRecord(ev[0], st);
-  if ((e = launch_exact_switch_posteriors(x, s, grid, st))) return hipfail(e, "exact_switch_posteriors");
-  hipEventRecord(ev[1], st);
-  if ((e = sync_st())) return hipfail(e, "exact_switch_posteriors");
-  float ms = 0;
-  hipEventElapsedTime(&ms, ev[0], ev[1]);
-  xp_ms_sites += ms;
-  return HMC_OK;
-}
-
-void Ctx::switch_list(SwitchList &sl) const {
-  const int n = nloc(), L = pan.L;
-  sl.off.assign((size_t)n + 1, 0);
-  sl.locus_a.clear();
-  sl.locus_b.clear();
-  for (int i = 0; i < n; ++i) {
-    const uint8_t *g0 = pan.idx.data() + ((size_t)(i0 + i) * 2) * L, *g1 = g0 + L;
-    int last = -1;  // the heterozygous locus before k
-    for (int k = 0; k < L; ++k) {
-      if (g0[k] == MISSING || g1[k] == MISSING || g0[k] == g1[k]) continue;
-      if (last >= 0) {
-        sl.locus_a.push_back(last);
-        sl.locus_b.push_back(k);
-      }
-      last = k;
-    }
-    sl.off[i + 1] = sl.locus_a.size();
-  }
-}
-
-int Ctx::switch_posteriors(int32_t *indiv, int32_t *locus_a, int32_t *locus_b, int32_t *status, double *post,
-                           const SwitchList *pre) {
-  if (!have_estep) return fail(HMC_EARG, "switch posteriors need an E-step first (hmc_resolve_all)");
-  if (estep_gen != model_gen)
-    return fail(HMC_EARG, "switch posteriors: the model changed since the last E-step (hmc_resolve_all again)");
-  if (pan.amax > 44) return fail(HMC_EUNSUPPORTED, "switch posteriors with more than 44 alleles per locus");
-  const int n = nloc();
-  SwitchList own;
-  if (!pre) switch_list(own);
-  const SwitchList &sl = pre ? *pre : own;
-  const size_t ns = sl.locus_a.size();
-  n_switch_last = ns;
-  sw_ms_struct = sw_ms_fb = sw_ms_sweep = 0;
-  sw_groups = sw_pruned = sw_spilled = 0;
-  if (indiv)
-    for (int i = 0; i < n; ++i)
-      for (unsigned long long q = sl.off[i]; q < sl.off[i + 1]; ++q) indiv[q] = i0 + i;
-  if (locus_a && ns) std::copy(sl.locus_a.begin(), sl.locus_a.end(), locus_a);
-  if (locus_b && ns) std::copy(sl.locus_b.begin(), sl.locus_b.end(), locus_b);
-  if (ns == 0) return HMC_OK;
-  hipError_t er;
-  if ((er = d_site_off.ensure((size_t)n + 1)) || (er = d_sw_a.ensure(ns)) || (er = d_sw_b.ensure(ns)) ||
-      (er = d_site_status.ensure(ns)) || (er = d_site_post.ensure(ns * 2)) || (er = d_xstatus.ensure(n)) ||
-      (er = d_xre.ensure(n)) || (er = d_xfmax.ensure(n)) ||
-      (er = hipMemcpyAsync(d_site_off.p, sl.off.data(), ((size_t)n + 1) * 8, hipMemcpyHostToDevice, st)) ||
-      (er = hipMemcpyAsync(d_sw_a.p, sl.locus_a.data(), ns * 4, hipMemcpyHostToDevice, st)) ||
-      (er = hipMemcpyAsync(d_sw_b.p, sl.locus_b.data(), ns * 4, hipMemcpyHostToDevice, st)) ||
-      (er = hipMemsetAsync(d_site_post.p, 0, ns * 2 * 8, st)) || (er = hipMemsetAsync(d_site_status.p, 0, ns * 4, st)))
-    return hipfail(er, "switch posteriors");
-  // the pass counts in the genotype posteriors' fields: theirs are put back
-  const double g_struct = xp_ms_struct, g_fb = xp_ms_fb, g_sites = xp_ms_sites;
-  const int g_groups = xp_groups, g_pruned = xp_pruned;
-  const int rc = xp_pass(XP_SWITCH, "switch posteriors");
-  sw_ms_struct = xp_ms_struct;
-  sw_ms_fb = xp_ms_fb;
-  sw_ms_sweep = xp_ms_sites;
-  sw_groups = xp_groups;
-  sw_pruned = xp_pruned;
-  xp_ms_struct = g_struct;
-  xp_ms_fb = g_fb;
-  xp_ms_sites = g_sites;
-  xp_groups = g_groups;
-  xp_pruned = g_pruned;
-  if (rc) return rc;
-  if ((status && (er = hipMemcpyAsync(status, d_site_status.p, ns * 4, hipMemcpyDeviceToHost, st))) ||
-      (post && (er = hipMemcpyAsync(post, d_site_post.p, ns * 2 * 8, hipMemcpyDeviceToHost, st))) || (er = sync_st()))
-    return hipfail(er, "switch posteriors");
-  return HMC_OK;
-}
-
-int Ctx::pair_group(const ExactArgs &x, const int32_t *ids, const std::vector<int32_t> &fm, int k, int dev_cu) {
-  const int NS = pr_ns_run;
-  PairArgs s;
-  s.row_off = d_site_off.p;
-  s.ev_off = d_pr_evoff.p;
-  s.ev = d_pr_ev.p;
-  s.post = d_site_post.p;
-  s.row_status = d_site_status.p;
-  s.tier = pr_tier > 0 ? pr_tier : PAIR_TIER_DEFAULT;
-  s.lds_states = std::max(1, std::min(s.tier, x.fmax));  // no more LDS than the group's largest record asks for
-  int grid = std::max(1, std::min(k, dev_cu * 8));
-  hipError_t e;
-  int spilled = 0;
-  for (int q = 0; q < k; ++q) spilled += fm[ids[q]] > s.tier;
-  pr_spilled += spilled;
-  if (spilled) {  // frontiers past the tier: 32 NS B per state and block in HBM, at most 1 GiB (the grid does not change the bits)
-    grid = (int)std::max<size_t>(1, std::min<size_t>((size_t)grid, ((size_t)1 << 30) / ((size_t)32 * NS * x.fmax)));
-    if ((e = d_pr_scratch.ensure((size_t)grid * 4 * NS * x.fmax))) return hipfail(e, "exact_pair_posteriors");
-    s.scratch = d_pr_scratch.p;
-    s.scratch_states = x.fmax;
-  }
-  hipEventRecord(ev[0], st);
-  if ((e = launch_exact_pair_posteriors(x, s, NS, grid, st))) return hipfail(e, "exact_pair_posteriors");
-  hipEventRecord(ev[1], st);
-  if ((e = sync_st())) return hipfail(e, "exact_pair_posteriors");
-  float ms = 0;
-  hipEventElapsedTime(&ms, ev[0], ev[1]);
-  xp_ms_sites += ms;
-  return HMC_OK;
-}
-
-void Ctx::pair_span_list(int span, std::vector<int32_t> &indiv, std::vector<int32_t> &locus_a,
-                         std::vector<int32_t> &locus_b) const {
-  const int n = nloc(), L = pan.L;
-  indiv.clear();
-  locus_a.clear();
-  locus_b.clear();
-  std::vector<int32_t> het;
-  for (int i = 0; i < n; ++i) {
-    const uint8_t *g0 = pan.idx.data() + ((size_t)(i0 + i) * 2) * L, *g1 = g0 + L;
-    het.clear();
-    for (int k = 0; k < L; ++k)
-      if (g0[k] != MISSING && g1[k] != MISSING && g0[k] != g1[k]) het.push_back(k);
-    for (size_t q = 0; q < het.size(); ++q)
-      for (size_t d = 1; d <= (size_t)span && q + d < het.size(); ++d) {
-        indiv.push_back(i0 + i);
-        locus_a.push_back(het[q]);
-        locus_b.push_back(het[q + d]);
-      }
-  }
-}
-
-int Ctx::pair_plan(int64_t nq, const int32_t *indiv, const int32_t *locus_a, const int32_t *locus_b, int ns, PairPlan &pl) {
-  const int n = nloc(), L = pan.L, hl = head_len;
-  for (int64_t q = 0; q < nq; ++q) {
-    const int i = indiv[q], a = locus_a[q], b = locus_b[q];
-    if (i < i0 || i >= i1)
-      return fail(HMC_EARG, "pair posteriors: query %lld: individual %d is outside this rank's shard [%d, %d)", (long long)q, i,
-                  i0, i1);
-    if (a < 0 || a >= L || b < 0 || b >= L)
-      return fail(HMC_EARG, "pair posteriors: query %lld: loci (%d, %d) outside [0, %d)", (long long)q, a, b, L);
-    if (a >= b) return fail(HMC_EARG, "pair posteriors: query %lld: locus_a %d is not below locus_b %d", (long long)q, a, b);
-    const uint8_t *g0 = pan.idx.data() + ((size_t)i * 2) * L, *g1 = g0 + L;
-    for (int k : {a, b})
-      if (g0[k] == MISSING || g1[k] == MISSING || g0[k] == g1[k])
-        return fail(HMC_EARG, "pair posteriors: query %lld: locus %d of individual %d is not heterozygous in the input",
-                    (long long)q, k, i);
-  }
-  // the caller's queries sorted by (individual, a, b); the distinct ones are the rows
-  std::vector<size_t> ord((size_t)nq);
-  for (size_t q = 0; q < ord.size(); ++q) ord[q] = q;
-  auto key_less = [&](size_t x, size_t y) {
-    if (indiv[x] != indiv[y]) return indiv[x] < indiv[y];
-    if (locus_a[x] != locus_a[y]) return locus_a[x] < locus_a[y];
-    return locus_b[x] < locus_b[y];
-  };
-  std::sort(ord.begin(), ord.end(), key_less);
-  pl.row_off.assign((size_t)n + 1, 0);
-  pl.ev_off.assign((size_t)n + 1, 0);
-  pl.row_a.clear();
-  pl.row_b.clear();
-  pl.row_of.assign((size_t)nq, 0);
-  pl.ev.clear();
-  pl.need = pl.rounds = 0;
-  auto rec_of = [&](int k) { return k < hl ? hl : k + 1; };
-  struct Anchor {
-    int a, ja, jend, round, slot;
-    size_t r0, r1;  // its rows
-  };
-  struct Keyed {  // execution order within a round (exact.hpp, PairEvent)
-    int rec, phase, a, kind, b;
-    PairEvent ev;
-  };
-  std::vector<Anchor> anchors;
-  std::vector<std::vector<int>> busy;  // [round][slot]: the record at which the slot's holder is freed
-  std::vector<int> ends;               // the intervals' last records, for the number of anchors live at once
-  std::vector<Keyed> evs;
-  size_t p = 0;
-  for (int i = 0; i < n; ++i) {
-    const size_t row0 = pl.row_a.size();
-    anchors.clear();
-    for (; p < ord.size() && indiv[ord[p]] == i0 + i; ++p) {
-      const int a = locus_a[ord[p]], b = locus_b[ord[p]];
-      if (pl.row_a.size() == row0 || pl.row_a.back() != a || pl.row_b.back() != b) {
-        pl.row_a.push_back(a);
-        pl.row_b.push_back(b);
-        if (anchors.empty() || anchors.back().a != a) anchors.push_back({a, rec_of(a), 0, 0, 0, pl.row_a.size() - 1, 0});
-        anchors.back().jend = rec_of(b);  // rows ascend in b: the last one is the farthest
-        anchors.back().r1 = pl.row_a.size();
-      }
-      pl.row_of[ord[p]] = pl.row_a.size() - 1;
-    }
-    pl.row_off[i + 1] = pl.row_a.size();
-    // a slot is free for an anchor at record ja when its holder's last record is at most ja: at a record the
-    // carried-in anchors are evaluated and freed before new ones start, and head-only anchors end in turn
-    busy.clear();
-    ends.clear();
-    int rounds = 0;
-    for (Anchor &an : anchors) {
-      ends.erase(std::remove_if(ends.begin(), ends.end(), [&](int e) { return e <= an.ja; }), ends.end());
-      ends.push_back(an.jend);
-      pl.need = std::max(pl.need, (int)ends.size());
-      bool placed = false;
-      for (size_t r = 0; !placed; ++r) {
-        if (r == busy.size()) busy.push_back(std::vector<int>((size_t)ns, 0));
-        for (int sl = 0; sl < ns && !placed; ++sl)
-          if (busy[r][sl] <= an.ja) {
-            busy[r][sl] = an.jend;
-            an.round = (int)r;
-            an.slot = sl;
-            placed = true;
-          }
-      }
-      rounds = std::max(rounds, an.round + 1);
-    }
-    pl.rounds = std::max(pl.rounds, rounds);
-    for (int r = 0; r < rounds; ++r) {
-      evs.clear();
-      for (const Anchor &an : anchors) {
-        if (an.round != r) continue;
-        evs.push_back({an.ja, 1, an.a, 0, 0, {an.ja, PAIR_EV_ANCHOR | an.slot << 2, an.a, -1}});
-        for (size_t w = an.r0; w < an.r1; ++w) {
-          const int b = pl.row_b[w], jb = rec_of(b);
-          const PairEvent e{jb, PAIR_EV_EVAL | an.slot << 2, b, (int32_t)(w - row0)};
-          if (jb == an.ja) evs.push_back({jb, 1, an.a, 1, b, e});  // both inside the head
-          else evs.push_back({jb, 0, 0, 0, b, e});
-        }
-        const PairEvent f{an.jend, PAIR_EV_FREE | an.slot << 2, an.a, -1};
-        if (an.jend == an.ja) evs.push_back({an.jend, 1, an.a, 2, 0, f});
-        else evs.push_back({an.jend, 0, 0, 1, an.a, f});
-      }
-      std::sort(evs.begin(), evs.end(), [](const Keyed &x, const Keyed &y) {
-        return std::tie(x.rec, x.phase, x.a, x.kind, x.b, x.ev.op) < std::tie(y.rec, y.phase, y.a, y.kind, y.b, y.ev.op);
-      });
-      for (const Keyed &k : evs) pl.ev.push_back(k.ev);
-    }
-    pl.ev_off[i + 1] = pl.ev.size();
-  }
-  return HMC_OK;
-}
-
-int Ctx::pair_posteriors(int64_t nq, const int32_t *indiv, const int32_t *locus_a, const int32_t *locus_b, int32_t *status,
-                         double *post) {
-  if (!have_estep) return fail(HMC_EARG, "pair posteriors need an E-step first (hmc_resolve_all)");
-  if (estep_gen != model_gen)
-    return fail(HMC_EARG, "pair posteriors: the model changed since the last E-step (hmc_resolve_all again)");
-  if (pan.amax > 44) return fail(HMC_EUNSUPPORTED, "pair posteriors with more than 44 alleles per locus");
-  if (nq < 0 || (nq > 0 && (!indiv || !locus_a || !locus_b))) return fail(HMC_EARG, "pair posteriors: no queries given");
-  pr_ms_struct = pr_ms_fb = pr_ms_sweep = 0;
-  pr_groups = pr_pruned = pr_spilled = pr_ns = pr_rounds = 0;
-  if (nq == 0) return HMC_OK;
-  const int n = nloc();
-  PairPlan pl;
-  int rc;
-  // NS: as asked, else the smallest instantiated that holds every individual's anchors in one round (8 at most)
-  int NS = pr_slots;
-  if (NS == 0) {
-    if ((rc = pair_plan(nq, indiv, locus_a, locus_b, PAIR_SLOTS_MAX, pl))) return rc;
-    NS = pl.need <= 1 ? 1 : pl.need <= 2 ? 2 : pl.need <= 4 ? 4 : 8;
-  }
-  if (NS != PAIR_SLOTS_MAX || pr_slots) {
-    if ((rc = pair_plan(nq, indiv, locus_a, locus_b, NS, pl))) return rc;
-  }
-  pr_ns = pr_ns_run = NS;
-  pr_rounds = pl.rounds;
-  const size_t nr = pl.row_a.size(), ne = pl.ev.size();
-  hipError_t er;
-  if ((er = d_site_off.ensure((size_t)n + 1)) || (er = d_pr_evoff.ensure((size_t)n + 1)) || (er = d_pr_ev.ensure(ne)) ||
-      (er = d_site_status.ensure(nr)) || (er = d_site_post.ensure(nr * 2)) || (er = d_xstatus.ensure(n)) ||
-      (er = d_xre.ensure(n)) || (er = d_xfmax.ensure(n)) ||
-      (er = hipMemcpyAsync(d_site_off.p, pl.row_off.data(), ((size_t)n + 1) * 8, hipMemcpyHostToDevice, st)) ||
-      (er = hipMemcpyAsync(d_pr_evoff.p, pl.ev_off.data(), ((size_t)n + 1) * 8, hipMemcpyHostToDevice, st)) ||
-      (er = hipMemcpyAsync(d_pr_ev.p, pl.ev.data(), ne * sizeof(PairEvent), hipMemcpyHostToDevice, st)) ||
-      (er = hipMemsetAsync(d_site_post.p, 0, nr * 2 * 8, st)) || (er = hipMemsetAsync(d_site_status.p, 0, nr * 4, st)))
-    return hipfail(er, "pair posteriors");
-  // the pass counts in the genotype posteriors' fields: theirs are put back
-  const double g_struct = xp_ms_struct, g_fb = xp_ms_fb, g_sites = xp_ms_sites;
-  const int g_groups = xp_groups, g_pruned = xp_pruned;
-  rc = xp_pass(XP_PAIR, "pair posteriors");
-  pr_ms_struct = xp_ms_struct;
-  pr_ms_fb = xp_ms_fb;
-  pr_ms_sweep = xp_ms_sites;
-  pr_groups = xp_groups;
-  pr_pruned = xp_pruned;
-  xp_ms_struct = g_struct;
-  xp_ms_fb = g_fb;
-  xp_ms_sites = g_sites;
-  xp_groups = g_groups;
-  xp_pruned = g_pruned;
-  if (rc) return rc;
-  std::vector<int32_t> rst(nr);
-  std::vector<double> rpost(nr * 2);
-  if ((er = hipMemcpyAsync(rst.data(), d_site_status.p, nr * 4, hipMemcpyDeviceToHost, st)) ||
-      (er = hipMemcpyAsync(rpost.data(), d_site_post.p, nr * 2 * 8, hipMemcpyDeviceToHost, st)) || (er = sync_st()))
-    return hipfail(er, "pair posteriors");
-  for (int64_t q = 0; q < nq; ++q) {  // rows in the caller's order
-    const size_t r = pl.row_of[(size_t)q];
-    if (status) status[q] = rst[r];
-    if (post) {
-      post[2 * q] = rpost[2 * r];
-      post[2 * q + 1] = rpost[2 * r + 1];
-    }
-  }
-  return HMC_OK;
-}
-
-int Ctx::draw_group(const ExactArgs &x, const int32_t *ids, int k, int dev_cu) {
-  const int L = pan.L, D = dr.draws, A = pan.amax;
-  std::vector<int32_t> sel;  // the group's individuals that the caller asked for
-  for (int q = 0; q < k; ++q)
-    if (dr.row_off[ids[q] + 1] > dr.row_off[ids[q]]) sel.push_back(ids[q]);
-  if (sel.empty()) return HMC_OK;
-  const size_t per = (size_t)2 * L * D;   // haplotype entries of one individual
-  // device output of one individual: prob, the draw-minor bytes and the symbols
-  const size_t dev_bytes = (size_t)D * 8 + (dr.hap ? per * 5 : 0);
-  const size_t cap = std::max<size_t>(1, DRAW_OUT_BYTES / dev_bytes);
-  const int ndc = (D + DRAW_BLOCK - 1) / DRAW_BLOCK;
-  const int nchunks = (std::max(x.fmax, 1) + WAVE - 1) / WAVE;
-  const int lds_chunks = dr_lds_chunks < 0 ? DRAW_LDS_CHUNKS : std::min(dr_lds_chunks, DRAW_LDS_CHUNKS);
-  hipError_t e;
-  std::vector<int32_t> symtab((size_t)L * A, -1);  // the panel's symbol table, [locus][allele index]
-  for (int l = 0; l < L; ++l)
-    for (size_t j = 0; j < pan.sym[l].size(); ++j) symtab[(size_t)l * A + j] = pan.sym[l][j].first;
-  if (dr.hap &&
-      ((e = d_dr_sym.ensure(symtab.size())) ||
-       (e = hipMemcpyAsync(d_dr_sym.p, symtab.data(), symtab.size() * 4, hipMemcpyHostToDevice, st)) || (e = sync_st())))
-    return hipfail(e, "exact_posterior_draws");
-  std::vector<int32_t> h_st;
-  std::vector<double> h_prob;
-  for (size_t pos = 0; pos < sel.size(); pos += cap) {
-    const int nb = (int)std::min(cap, sel.size() - pos);
-    const int grid = (int)std::max<long long>(1, std::min<long long>((long long)nb * ndc, (long long)dev_cu * 8));
-    ExactArgs xb = x;
-    DrawArgs s;
-    if ((e = d_dr_order.ensure(nb)) || (e = d_dr_status.ensure(nb)) || (e = d_dr_prob.ensure((size_t)nb * D)) ||
-        (dr.hap && (e = d_dr_al.ensure((size_t)nb * per))) || (dr.hap && (e = d_dr_hap.ensure((size_t)nb * per))) ||
-        (nchunks > lds_chunks && (e = d_dr_csum.ensure((size_t)grid * nchunks))) ||
-        (e = hipMemsetAsync(d_dr_status.p, 0, (size_t)nb * 4, st)))  // the kernel writes the non-zero ones
-      return hipfail(e, "exact_posterior_draws");
-    int rc;
-    if ((rc = upload_order(d_dr_order, sel.data() + pos, nb))) return rc;
-    xb.order = d_dr_order.p;
-    xb.n_order = nb;
-    s.draws = D;
-    s.seed = dr.seed;
-    s.indiv0 = i0;
-    s.al = dr.hap ? d_dr_al.p : nullptr;
-    s.prob = d_dr_prob.p;
-    s.status = d_dr_status.p;
-    s.lds_chunks = lds_chunks;
-    if (nchunks > lds_chunks) {
-      s.csum = d_dr_csum.p;
-      s.csum_stride = nchunks;
-    }
-    hipEventRecord(ev[0], st);
-    if ((e = launch_exact_posterior_draws(xb, s, grid, st))) return hipfail(e, "exact_posterior_draws");
-    if (dr.hap && (e = launch_draws_to_symbols(d_dr_al.p, d_dr_sym.p, d_dr_hap.p, nb, L, D, A, st)))
-      return hipfail(e, "draws_to_symbols");
-    hipEventRecord(ev[1], st);
-    h_st.resize(nb);
-    h_prob.resize((size_t)nb * D);
-    if ((e = hipMemcpyAsync(h_st.data(), d_dr_status.p, (size_t)nb * 4, hipMemcpyDeviceToHost, st)) ||
-        (e = hipMemcpyAsync(h_prob.data(), d_dr_prob.p, (size_t)nb * D * 8, hipMemcpyDeviceToHost, st)) ||
-        (e = sync_st()))
-      return hipfail(e, "exact_posterior_draws");
-    float ms = 0;
-    hipEventElapsedTime(&ms, ev[0], ev[1]);
-    xp_ms_sites += ms;
-    if (dr.hap) {  // each individual's symbols straight into the first of the caller's rows that ask for it
-      for (int u = 0; u < nb; ++u)
-        if (h_st[u] == 0 && (e = hipMemcpyAsync(dr.hap + (size_t)dr.rows[dr.row_off[sel[pos + u]]] * per, d_dr_hap.p + (size_t)u * per,
-                                                per * 4, hipMemcpyDeviceToHost, st)))
-          return hipfail(e, "exact_posterior_draws");
-      if ((e = sync_st())) return hipfail(e, "exact_posterior_draws");
-    }
-    for (int u = 0; u < nb; ++u) {
-      const int bi = sel[pos + u];
-      dr.status[bi] = h_st[u];
-      if (h_st[u] != 0) continue;  // (the caller's rows get the input genotype)
-      int32_t *first = dr.hap ? dr.hap + (size_t)dr.rows[dr.row_off[bi]] * per : nullptr;
-      for (int64_t w = dr.row_off[bi]; w < dr.row_off[bi + 1]; ++w) {
-        const int64_t row = dr.rows[w];
-        if (dr.prob) std::copy(h_prob.begin() + (size_t)u * D, h_prob.begin() + (size_t)(u + 1) * D, dr.prob + row * D);
-        if (dr.hap && w > dr.row_off[bi]) std::copy(first, first + per, dr.hap + (size_t)row * per);  // a repeated individual
-      }
-    }
-  }
-  return HMC_OK;
-}
-
-int Ctx::map_group(const ExactArgs &x, const int32_t *ids, int k, int dev_cu) {
-  const int L = pan.L, A = pan.amax;
-  std::vector<int32_t> sel;  // the group's individuals that the caller asked for
-  for (int q = 0; q < k; ++q)
-    if (mp.row_off[ids[q] + 1] > mp.row_off[ids[q]]) sel.push_back(ids[q]);
-  if (sel.empty()) return HMC_OK;
-  const size_t per = (size_t)2 * L;  // haplotype entries of one individual
-  const size_t cap = std::max<size_t>(1, DRAW_OUT_BYTES / (8 + (mp.hap ? per * 5 : 0)));
-  hipError_t e;
-  std::vector<int32_t> symtab((size_t)L * A, -1);  // the panel's symbol table, [locus][allele index]
-  for (int l = 0; l < L; ++l)
-    for (size_t j = 0; j < pan.sym[l].size(); ++j) symtab[(size_t)l * A + j] = pan.sym[l][j].first;
-  if (mp.hap &&
-      ((e = d_dr_sym.ensure(symtab.size())) ||
-       (e = hipMemcpyAsync(d_dr_sym.p, symtab.data(), symtab.size() * 4, hipMemcpyHostToDevice, st)) || (e = sync_st())))
-    return hipfail(e, "exact_map_phase");
-  std::vector<int32_t> h_st, h_hap;
-  std::vector<double> h_prob;
-  for (size_t pos = 0; pos < sel.size(); pos += cap) {
-    const int nb = (int)std::min(cap, sel.size() - pos);
-    const int grid = std::max(1, std::min(nb, dev_cu * 8));
-    ExactArgs xb = x;
-    MapArgs s;
-    if ((e = d_dr_order.ensure(nb)) || (e = d_dr_status.ensure(nb)) || (e = d_dr_prob.ensure(nb)) ||
-        (mp.hap && (e = d_dr_al.ensure((size_t)nb * per))) || (mp.hap && (e = d_dr_hap.ensure((size_t)nb * per))) ||
-        (e = hipMemsetAsync(d_dr_status.p, 0, (size_t)nb * 4, st)) ||  // the kernel writes the non-zero ones
-        (mp.hap && (e = hipMemsetAsync(d_dr_al.p, 0xFF, (size_t)nb * per, st))))
-      return hipfail(e, "exact_map_phase");
-    int rc;
-    if ((rc = upload_order(d_dr_order, sel.data() + pos, nb))) return rc;
-    xb.order = d_dr_order.p;
-    xb.n_order = nb;
-    s.al = mp.hap ? d_dr_al.p : nullptr;
-    s.prob = d_dr_prob.p;
-    s.status = d_dr_status.p;
-    hipEventRecord(ev[0], st);
-    if ((e = launch_exact_map_phase(xb, s, grid, st))) return hipfail(e, "exact_map_phase");
-    if (mp.hap && (e = launch_draws_to_symbols(d_dr_al.p, d_dr_sym.p, d_dr_hap.p, nb, L, 1, A, st)))
-      return hipfail(e, "draws_to_symbols");
-    hipEventRecord(ev[1], st);
-    h_st.resize(nb);
-    h_prob.resize(nb);
-    h_hap.resize(mp.hap ? (size_t)nb * per : 0);
-    if ((e = hipMemcpyAsync(h_st.data(), d_dr_status.p, (size_t)nb * 4, hipMemcpyDeviceToHost, st)) ||
-        (e = hipMemcpyAsync(h_prob.data(), d_dr_prob.p, (size_t)nb * 8, hipMemcpyDeviceToHost, st)) ||
-        (mp.hap && (e = hipMemcpyAsync(h_hap.data(), d_dr_hap.p, (size_t)nb * per * 4, hipMemcpyDeviceToHost, st))) ||
-        (e = sync_st()))
-      return hipfail(e, "exact_map_phase");
-    float ms = 0;
-    hipEventElapsedTime(&ms, ev[0], ev[1]);
-    xp_ms_sites += ms;
-    for (int u = 0; u < nb; ++u) {
-      const int bi = sel[pos + u];
-      mp.status[bi] = h_st[u];
-      if (h_st[u] != 0) continue;  // (the caller's rows get the input genotype)
-      for (int64_t w = mp.row_off[bi]; w < mp.row_off[bi + 1]; ++w) {
-        const int64_t row = mp.rows[w];
-        if (mp.prob) mp.prob[row] = h_prob[u];
-        if (mp.hap) std::copy(h_hap.begin() + (size_t)u * per, h_hap.begin() + (size_t)(u + 1) * per, mp.hap + (size_t)row * per);
-      }
-    }
-  }
-  return HMC_OK;
-}
-
-int Ctx::ranked_group(const ExactArgs &x, const int32_t *ids, int k, int dev_cu) {
-  const int L = pan.L, A = pan.amax, K = rk.draws, KL = rank_width(K);
-  std::vector<int32_t> sel;  // the group's individuals that the caller asked for
-  for (int q = 0; q < k; ++q)
-    if (rk.row_off[ids[q] + 1] > rk.row_off[ids[q]]) sel.push_back(ids[q]);
-  if (sel.empty()) return HMC_OK;
-  const size_t per = (size_t)2 * L * K;  // haplotype entries of one individual
-  const size_t out_cap = std::max<size_t>(1, DRAW_OUT_BYTES / ((size_t)K * 8 + (rk.hap ? per * 5 : 0)));
-  hipError_t e;
-  int rc;
-  std::vector<int32_t> symtab((size_t)L * A, -1);  // the panel's symbol table, [locus][allele index]
-  for (int l = 0; l < L; ++l)
-    for (size_t j = 0; j < pan.sym[l].size(); ++j) symtab[(size_t)l * A + j] = pan.sym[l][j].first;
-  if (rk.hap &&
-      ((e = d_dr_sym.ensure(symtab.size())) ||
-       (e = hipMemcpyAsync(d_dr_sym.p, symtab.data(), symtab.size() * 4, hipMemcpyHostToDevice, st))))
-    return hipfail(e, "exact_ranked_phasings");
-  // the list store every individual needs: 24 KL bytes per state of its records and 8 per record
-  const int ns = (int)sel.size();
-  std::vector<unsigned long long> need(ns);
-  {
-    ExactArgs xt = x;
-    if ((e = d_dr_order.ensure(ns)) || (e = d_rk_total.ensure(ns))) return hipfail(e, "exact_ranked_phasings");
-    if ((rc = upload_order(d_dr_order, sel.data(), ns))) return rc;
-    xt.order = d_dr_order.p;
-    xt.n_order = ns;
-    if ((e = launch_exact_state_totals(xt, d_rk_total.p, st)) ||
-        (e = hipMemcpyAsync(need.data(), d_rk_total.p, (size_t)ns * 8, hipMemcpyDeviceToHost, st)) || (e = sync_st()))
-      return hipfail(e, "exact_ranked_phasings");
-    for (int u = 0; u < ns; ++u) need[u] = rank_store_bytes(KL, need[u], L + 1 - head_len);
-  }
-  // An individual's lists are 1.5 KL times its values, which fit the value store: alone in a batch it may take
-  // that multiple of the budget, so that no individual the forward pass held is refused for its lists.
-  const uint64_t budget = rank_budget_bytes(), alone = budget / 2 * 3 * (uint64_t)KL;
-  std::vector<int32_t> h_st, h_cnt, h_hap;
-  std::vector<double> h_prob;
-  std::vector<unsigned long long> sbase;
-  for (size_t pos = 0; pos < sel.size();) {
-    // a batch: individuals in order while their lists fit the budget (and the outputs theirs)
-    uint64_t bytes = 0;
-    int nb = 0;
-    sbase.clear();
-    while (pos + nb < sel.size() && (size_t)nb < out_cap && (nb == 0 || bytes + need[pos + nb] <= budget)) {
-      if (need[pos + nb] > alone)
-        return fail(HMC_ENOMEM, "ranked phasings: the lists of individual %d need %llu bytes at width %d (list store budget %llu)",
-                    i0 + sel[pos + nb], (unsigned long long)need[pos + nb], KL, (unsigned long long)budget);
-      sbase.push_back(bytes);
-      bytes += need[pos + nb];
-      ++nb;
-    }
-    const int grid = std::max(1, std::min(nb, dev_cu * 8));
-    ExactArgs xb = x;
-    RankArgs s;
-    if ((e = d_dr_order.ensure(nb)) || (e = d_dr_status.ensure(nb)) || (e = d_rk_count.ensure(nb)) || (e = d_rk_base.ensure(nb)) ||
-        (e = d_dr_prob.ensure((size_t)nb * K)) || (e = d_rk_store.ensure(std::max<size_t>(bytes, 8))) ||
-        (rk.hap && (e = d_dr_al.ensure((size_t)nb * per))) || (rk.hap && (e = d_dr_hap.ensure((size_t)nb * per))) ||
-        (e = hipMemsetAsync(d_dr_status.p, 0, (size_t)nb * 4, st)) ||  // the kernel writes the non-zero ones
-        (e = hipMemsetAsync(d_rk_count.p, 0, (size_t)nb * 4, st)) ||
-        (e = hipMemsetAsync(d_dr_prob.p, 0, (size_t)nb * K * 8, st)) ||  // rows past an individual's count: prob 0
-        (rk.hap && (e = hipMemsetAsync(d_dr_al.p, 0xFF, (size_t)nb * per, st))) ||
-        (e = hipMemcpyAsync(d_rk_base.p, sbase.data(), (size_t)nb * 8, hipMemcpyHostToDevice, st)))
-      return hipfail(e, "exact_ranked_phasings");
-    if ((rc = upload_order(d_dr_order, sel.data() + pos, nb))) return rc;
-    xb.order = d_dr_order.p;
-    xb.n_order = nb;
-    s.k = K;
-    s.al = rk.hap ? d_dr_al.p : nullptr;
-    s.prob = d_dr_prob.p;
-    s.count = d_rk_count.p;
-    s.status = d_dr_status.p;
-    s.store = d_rk_store.p;
-    s.store_base = d_rk_base.p;
-    hipEventRecord(ev[0], st);
-    if ((e = launch_exact_ranked_phasings(xb, s, KL, grid, st))) return hipfail(e, "exact_ranked_phasings");
-    if (rk.hap && (e = launch_draws_to_symbols(d_dr_al.p, d_dr_sym.p, d_dr_hap.p, nb, L, K, A, st)))
-      return hipfail(e, "draws_to_symbols");
-    hipEventRecord(ev[1], st);
-    h_st.resize(nb);
-    h_cnt.resize(nb);
-    h_prob.resize((size_t)nb * K);
-    h_hap.resize(rk.hap ? (size_t)nb * per : 0);
-    if ((e = hipMemcpyAsync(h_st.data(), d_dr_status.p, (size_t)nb * 4, hipMemcpyDeviceToHost, st)) ||
-        (e = hipMemcpyAsync(h_cnt.data(), d_rk_count.p, (size_t)nb * 4, hipMemcpyDeviceToHost, st)) ||
-        (e = hipMemcpyAsync(h_prob.data(), d_dr_prob.p, (size_t)nb * K * 8, hipMemcpyDeviceToHost, st)) ||
-        (rk.hap && (e = hipMemcpyAsync(h_hap.data(), d_dr_hap.p, (size_t)nb * per * 4, hipMemcpyDeviceToHost, st))) ||
-        (e = sync_st()))
-      return hipfail(e, "exact_ranked_phasings");
-    float ms = 0;
-    hipEventElapsedTime(&ms, ev[0], ev[1]);
-    xp_ms_sites += ms;
-    ++rk_batches;
-    for (int u = 0; u < nb; ++u) {
-      const int bi = sel[pos + u];
-      rk.status[bi] = h_st[u];
-      if (h_st[u] != 0) continue;  // (the caller's rows get the input genotype)
-      rk_count[bi] = h_cnt[u];
-      for (int64_t w = rk.row_off[bi]; w < rk.row_off[bi + 1]; ++w) {
-        const int64_t row = rk.rows[w];
-        if (rk.prob) std::copy(h_prob.begin() + (size_t)u * K, h_prob.begin() + (size_t)(u + 1) * K, rk.prob + (size_t)row * K);
-        if (rk.hap) std::copy(h_hap.begin() + (size_t)u * per, h_hap.begin() + (size_t)(u + 1) * per, rk.hap + (size_t)row * per);
-      }
-    }
-    pos += (size_t)nb;
-  }
-  return HMC_OK;
-}
-
-int Ctx::dosage_group(const ExactArgs &x, const int32_t *ids, const std::vector<int32_t> &fm, int k, int dev_cu) {
-  const int NS = ds_ns_run, P = ds.P;
-  std::vector<int32_t> sel;  // the group's individuals that the caller asked for
-  for (int q = 0; q < k; ++q)
-    if (ds.row_off[ids[q] + 1] > ds.row_off[ids[q]]) sel.push_back(ids[q]);
-  if (sel.empty()) return HMC_OK;
-  const size_t cap = std::max<size_t>(1, DOSE_OUT_BYTES / ((size_t)P * 8));  // individuals per batch of output rows
-  DoseArgs s;
-  s.ev = d_ds_ev.p;
-  s.n_events = ds.n_events;
-  s.codes = d_ds_codes.p;
-  s.n_patterns = P;
-  s.maxlen = ds.maxlen;
-  s.tier = ds_tier > 0 ? ds_tier : PAIR_TIER_DEFAULT;
-  s.lds_states = std::max(1, std::min(s.tier, x.fmax));  // no more LDS than the group's largest record asks for
-  hipError_t e;
-  int spilled = 0;
-  for (int bi : sel) spilled += fm[bi] > s.tier;
-  ds_spilled += spilled;
-  std::vector<int32_t> h_st;
-  std::vector<double> h_out;
-  for (size_t pos = 0; pos < sel.size(); pos += cap) {
-    const int nb = (int)std::min(cap, sel.size() - pos);
-    int grid = std::max(1, std::min(nb, dev_cu * 8));
-    if (spilled) {  // frontiers past the tier: 32 NS B per state and block in HBM, at most 1 GiB (the grid does not change the bits)
-      grid = (int)std::max<size_t>(1, std::min<size_t>((size_t)grid, ((size_t)1 << 30) / ((size_t)32 * NS * x.fmax)));
-      if ((e = d_ds_scratch.ensure((size_t)grid * 4 * NS * x.fmax))) return hipfail(e, "exact_haplotype_dosages");
-      s.scratch = d_ds_scratch.p;
-      s.scratch_states = x.fmax;
-    }
-    if ((e = d_ds_order.ensure(nb)) || (e = d_ds_status.ensure(nb)) || (e = d_ds_out.ensure((size_t)nb * P)) ||
-        (e = hipMemsetAsync(d_ds_status.p, 0, (size_t)nb * 4, st)) || (e = hipMemsetAsync(d_ds_out.p, 0, (size_t)nb * P * 8, st)))
-      return hipfail(e, "exact_haplotype_dosages");
-    int rc;
-    if ((rc = upload_order(d_ds_order, sel.data() + pos, nb))) return rc;
-    ExactArgs xb = x;
-    xb.order = d_ds_order.p;
-    xb.n_order = nb;
-    s.dosage = d_ds_out.p;
-    s.status = d_ds_status.p;
-    hipEventRecord(ev[0], st);
-    if ((e = launch_exact_haplotype_dosages(xb, s, NS, grid, st))) return hipfail(e, "exact_haplotype_dosages");
-    hipEventRecord(ev[1], st);
-    h_st.resize(nb);
-    h_out.resize((size_t)nb * P);
-    if ((e = hipMemcpyAsync(h_st.data(), d_ds_status.p, (size_t)nb * 4, hipMemcpyDeviceToHost, st)) ||
-        (e = hipMemcpyAsync(h_out.data(), d_ds_out.p, (size_t)nb * P * 8, hipMemcpyDeviceToHost, st)) || (e = sync_st()))
-      return hipfail(e, "exact_haplotype_dosages");
-    float ms = 0;
-    hipEventElapsedTime(&ms, ev[0], ev[1]);
-    xp_ms_sites += ms;
-    for (int u = 0; u < nb; ++u) {
-      const int bi = sel[pos + u];
-      ds.status[bi] = h_st[u];
-      if (h_st[u] != 0 || !ds.dosage) continue;  // (the caller's rows get zeros)
-      for (int64_t w = ds.row_off[bi]; w < ds.row_off[bi + 1]; ++w)
-        std::copy(h_out.begin() + (size_t)u * P, h_out.begin() + (size_t)(u + 1) * P, ds.dosage + (size_t)ds.rows[w] * P);
-    }
-  }
-  return HMC_OK;
-}
-
-int Ctx::haplotype_dosages(int64_t n, const int32_t *indiv, int n_patterns, const int32_t *start, const int32_t *len, int maxlen,
-                           const int32_t *alleles_a, const int32_t *alleles_b, double *dosage, int32_t *status) {
-  if (!have_estep) return fail(HMC_EARG, "haplotype dosages need an E-step first (hmc_resolve_all)");
-  if (estep_gen != model_gen)
-    return fail(HMC_EARG, "haplotype dosages: the model changed since the last E-step (hmc_resolve_all again)");
-  if (pan.amax > 44) return fail(HMC_EUNSUPPORTED, "haplotype dosages with more than 44 alleles per locus");
-  const int nl = nloc(), L = pan.L, P = n_patterns;
-  if (!indiv) n = nl;
-  if (n < 0) return fail(HMC_EARG, "haplotype dosages: n = %lld is negative", (long long)n);
-  if (P < 0 || (P > 0 && (!start || !len || !alleles_a))) return fail(HMC_EARG, "haplotype dosages: no patterns given");
-  for (int64_t q = 0; indiv && q < n; ++q)
-    if (indiv[q] < i0 || indiv[q] >= i1)
-      return fail(HMC_EARG, "haplotype dosages: entry %lld: individual %d is outside this rank's shard [%d, %d)", (long long)q,
-                  indiv[q], i0, i1);
-  for (int p = 0; p < P; ++p)
-    if (start[p] < 0 || len[p] < 1 || len[p] > maxlen || (long long)start[p] + len[p] > L)
-      return fail(HMC_EARG, "haplotype dosages: pattern %d: window start %d, length %d is outside [0, %d) or longer than maxlen %d",
-                  p, start[p], len[p], L, maxlen);
-  ds_ms_struct = ds_ms_fb = ds_ms_sweep = 0;
-  ds_groups = ds_pruned = ds_spilled = ds_ns = ds_rounds = 0;
-  if (n == 0 || P == 0) return HMC_OK;
-  // symbols to allele-table indices, one byte each
-  std::vector<uint8_t> codes((size_t)P * 2 * maxlen, (uint8_t)DOSE_ANY);
-  for (int p = 0; p < P; ++p)
-    for (int side = 0; side < 2; ++side) {
-      const int32_t *row = side ? alleles_b : alleles_a;
-      if (!row) continue;  // (row B not given: any allele everywhere)
-      for (int q = 0; q < len[p]; ++q) {
-        const int32_t sy = row[(size_t)p * maxlen + q];
-        if (sy == -1) continue;
-        const auto &tab = pan.sym[start[p] + q];
-        uint8_t c = (uint8_t)DOSE_ABSENT;
-        for (size_t j = 0; j < tab.size(); ++j)
-          if (tab[j].first == sy) c = (uint8_t)j;
-        codes[((size_t)p * 2 + side) * maxlen + q] = c;
-      }
-    }
-  // NS: as asked, else the smallest of 1, 2, 4 that runs the call in one round, else 4: on cfg 2 the sweep measured
-  // faster at NS = 4 in twice the rounds than at NS = 8 (14.1-14.7 against 14.6-15.3 ms on windows stepping 8,
-  // 47.8-48.2 against 56.5-57.1 ms on windows stepping 2; profiles/haplotype_dosages/README.md)
-  DosePlan pl;
-  int NS = ds_slots;
-  if (NS == 0) {
-    dose_plan(P, start, len, head_len, DOSE_SLOTS_AUTO_MAX, pl);
-    NS = pl.need <= 1 ? 1 : pl.need <= 2 ? 2 : DOSE_SLOTS_AUTO_MAX;
-  }
-  if (NS != DOSE_SLOTS_AUTO_MAX || ds_slots) dose_plan(P, start, len, head_len, NS, pl);
-  ds_ns = ds_ns_run = NS;
-  ds_rounds = pl.rounds;
-  auto local = [&](int64_t q) { return indiv ? indiv[q] - i0 : (int)q; };
-  ds.P = P;
-  ds.maxlen = maxlen;
-  ds.n_events = (int)pl.ev.size();
-  ds.dosage = dosage;
-  ds.row_off.assign((size_t)nl + 1, 0);
-  for (int64_t q = 0; q < n; ++q) ++ds.row_off[local(q) + 1];
-  for (int i = 0; i < nl; ++i) ds.row_off[i + 1] += ds.row_off[i];
-  ds.rows.assign((size_t)n, 0);
-  {
-    std::vector<int64_t> at(ds.row_off.begin(), ds.row_off.end() - 1);
-    for (int64_t q = 0; q < n; ++q) ds.rows[at[local(q)]++] = q;
-  }
-  ds.status.assign(nl, 1);
-  if (dosage) std::fill(dosage, dosage + (size_t)n * P, 0.0);
-  hipError_t er;
-  if ((er = d_xstatus.ensure(nl)) || (er = d_xre.ensure(nl)) || (er = d_xfmax.ensure(nl)) || (er = d_ds_ev.ensure(pl.ev.size())) ||
-      (er = d_ds_codes.ensure(codes.size())) ||
-      (er = hipMemcpyAsync(d_ds_ev.p, pl.ev.data(), pl.ev.size() * sizeof(DoseEvent), hipMemcpyHostToDevice, st)) ||
-      (er = hipMemcpyAsync(d_ds_codes.p, codes.data(), codes.size(), hipMemcpyHostToDevice, st)) || (er = sync_st()))
-    return hipfail(er, "haplotype dosages");
-  // the pass counts in the genotype posteriors' fields: theirs are put back
-  const double g_struct = xp_ms_struct, g_fb = xp_ms_fb, g_sites = xp_ms_sites;
-  const int g_groups = xp_groups, g_pruned = xp_pruned;
-  std::vector<char> asked(nl, 0);  // the passes run over the individuals asked for, not the whole shard
-  for (int i = 0; i < nl; ++i) asked[i] = ds.row_off[i + 1] > ds.row_off[i];
-  const int rc = xp_pass(XP_DOSE, "haplotype dosages", &asked);
-  ds_ms_struct = xp_ms_struct;
-  ds_ms_fb = xp_ms_fb;
-  ds_ms_sweep = xp_ms_sites;
-  ds_groups = xp_groups;
-  ds_pruned = xp_pruned;
-  xp_ms_struct = g_struct;
-  xp_ms_fb = g_fb;
-  xp_ms_sites = g_sites;
-  xp_groups = g_groups;
-  xp_pruned = g_pruned;
-  ds.dosage = nullptr;
-  if (rc) return rc;
-  for (int64_t q = 0; q < n; ++q) {
-    const int stt = ds.status[local(q)];
-    if (status) status[q] = stt;
-    // (a restarted pass may have left an earlier attempt's numbers in a row that ended unresolved)
-    if (stt != 0 && dosage) std::fill(dosage + (size_t)q * P, dosage + (size_t)(q + 1) * P, 0.0);
-  }
-  return HMC_OK;
-}
-
-int Ctx::posterior_draws(int64_t n, const int32_t *indiv, int draws, uint64_t seed, int32_t *hap, double *prob, int32_t *status) {
-  if (!have_estep) return fail(HMC_EARG, "posterior draws need an E-step first (hmc_resolve_all)");
-  if (estep_gen != model_gen)
-    return fail(HMC_EARG, "posterior draws: the model changed since the last E-step (hmc_resolve_all again)");
-  if (pan.amax > 44) return fail(HMC_EUNSUPPORTED, "posterior draws with more than 44 alleles per locus");
-  if (draws < 1) return fail(HMC_EARG, "posterior draws: draws = %d is below 1", draws);
-  const int nl = nloc(), L = pan.L;
-  if (!indiv) n = nl;
-  if (n < 0) return fail(HMC_EARG, "posterior draws: n = %lld is negative", (long long)n);
-  for (int64_t q = 0; indiv && q < n; ++q)
-    if (indiv[q] < i0 || indiv[q] >= i1)
-      return fail(HMC_EARG, "posterior draws: entry %lld: individual %d is outside this rank's shard [%d, %d)", (long long)q,
-                  indiv[q], i0, i1);
-  dr_ms_struct = dr_ms_fb = dr_ms_draw = 0;
-  dr_groups = dr_pruned = 0;
-  if (n == 0) return HMC_OK;
-  auto local = [&](int64_t q) { return indiv ? indiv[q] - i0 : (int)q; };
-  dr.draws = draws;
-  dr.seed = seed;
-  dr.hap = hap;
-  dr.prob = prob;
-  dr.row_off.assign((size_t)nl + 1, 0);
-  for (int64_t q = 0; q < n; ++q) ++dr.row_off[local(q) + 1];
-  for (int i = 0; i < nl; ++i) dr.row_off[i + 1] += dr.row_off[i];
-  dr.rows.assign((size_t)n, 0);
-  {
-    std::vector<int64_t> at(dr.row_off.begin(), dr.row_off.end() - 1);
-    for (int64_t q = 0; q < n; ++q) dr.rows[at[local(q)]++] = q;
-  }
-  dr.status.assign(nl, 1);
-  hipError_t er;
-  if ((er = d_xstatus.ensure(nl)) || (er = d_xre.ensure(nl)) || (er = d_xfmax.ensure(nl))) return hipfail(er, "posterior draws");
-  // the pass counts in the genotype posteriors' fields: theirs are put back
-  const double g_struct = xp_ms_struct, g_fb = xp_ms_fb, g_sites = xp_ms_sites;
-  const int g_groups = xp_groups, g_pruned = xp_pruned;
-  std::vector<char> asked(nl, 0);  // the passes run over the individuals asked for, not the whole shard
-  for (int i = 0; i < nl; ++i) asked[i] = dr.row_off[i + 1] > dr.row_off[i];
-  const int rc = xp_pass(XP_DRAW, "posterior draws", &asked);
-  dr_ms_struct = xp_ms_struct;
-  dr_ms_fb = xp_ms_fb;
-  dr_ms_draw = xp_ms_sites;
-  dr_groups = xp_groups;
-  dr_pruned = xp_pruned;
-  xp_ms_struct = g_struct;
-  xp_ms_fb = g_fb;
-  xp_ms_sites = g_sites;
-  xp_groups = g_groups;
-  xp_pruned = g_pruned;
-  dr.hap = nullptr;
-  dr.prob = nullptr;
-  if (rc) return rc;
-  for (int64_t q = 0; q < n; ++q) {
-    const int i = local(q), stt = dr.status[i];
-    if (status) status[q] = stt;
-    if (stt == 0) continue;
-    // unresolved, or P(genotype) subnormal: the input genotype, as hmc_get_resolutions gives it, at probability 0
-    if (prob) std::fill(prob + q * draws, prob + (q + 1) * draws, 0.0);
-    if (hap)
-      for (int d = 0; d < draws; ++d)
-        for (int side = 0; side < 2; ++side)
-          for (int l = 0; l < L; ++l)
-            hap[(((size_t)q * draws + d) * 2 + side) * L + l] = pan.symbol(l, pan.idx[((size_t)(i0 + i) * 2 + side) * L + l]);
-  }
-  return HMC_OK;
-}
-
-int Ctx::map_phase(int64_t n, const int32_t *indiv, int32_t *hap, double *prob, int32_t *status) {
-  if (!have_estep) return fail(HMC_EARG, "MAP phasing needs an E-step first (hmc_resolve_all)");
-  if (estep_gen != model_gen)
-    return fail(HMC_EARG, "MAP phasing: the model changed since the last E-step (hmc_resolve_all again)");
-  if (pan.amax > 44) return fail(HMC_EUNSUPPORTED, "MAP phasing with more than 44 alleles per locus");
-  const int nl = nloc(), L = pan.L;
-  if (!indiv) n = nl;
-  if (n < 0) return fail(HMC_EARG, "MAP phasing: n = %lld is negative", (long long)n);
-  for (int64_t q = 0; indiv && q < n; ++q)
-    if (indiv[q] < i0 || indiv[q] >= i1)
-      return fail(HMC_EARG, "MAP phasing: entry %lld: individual %d is outside this rank's shard [%d, %d)", (long long)q,
-                  indiv[q], i0, i1);
-  mp_ms_struct = mp_ms_fb = mp_ms_sweep = 0;
-  mp_groups = mp_pruned = 0;
-  if (n == 0) return HMC_OK;
-  auto local = [&](int64_t q) { return indiv ? indiv[q] - i0 : (int)q; };
-  mp.draws = 1;
-  mp.hap = hap;
-  mp.prob = prob;
-  mp.row_off.assign((size_t)nl + 1, 0);
-  for (int64_t q = 0; q < n; ++q) ++mp.row_off[local(q) + 1];
-  for (int i = 0; i < nl; ++i) mp.row_off[i + 1] += mp.row_off[i];
-  mp.rows.assign((size_t)n, 0);
-  {
-    std::vector<int64_t> at(mp.row_off.begin(), mp.row_off.end() - 1);
-    for (int64_t q = 0; q < n; ++q) mp.rows[at[local(q)]++] = q;
-  }
-  mp.status.assign(nl, 1);
-  hipError_t er;
-  if ((er = d_xstatus.ensure(nl)) || (er = d_xre.ensure(nl)) || (er = d_xfmax.ensure(nl))) return hipfail(er, "MAP phasing");
-  // the pass counts in the genotype posteriors' fields: theirs are put back
-  const double g_struct = xp_ms_struct, g_fb = xp_ms_fb, g_sites = xp_ms_sites;
-  const int g_groups = xp_groups, g_pruned = xp_pruned;
-  std::vector<char> asked(nl, 0);  // the passes run over the individuals asked for, not the whole shard
-  for (int i = 0; i < nl; ++i) asked[i] = mp.row_off[i + 1] > mp.row_off[i];
-  const int rc = xp_pass(XP_MAP, "MAP phasing", &asked);
-  mp_ms_struct = xp_ms_struct;
-  mp_ms_fb = xp_ms_fb;
-  mp_ms_sweep = xp_ms_sites;
-  mp_groups = xp_groups;
-  mp_pruned = xp_pruned;
-  xp_ms_struct = g_struct;
-  xp_ms_fb = g_fb;
-  xp_ms_sites = g_sites;
-  xp_groups = g_groups;
-  xp_pruned = g_pruned;
-  mp.hap = nullptr;
-  mp.prob = nullptr;
-  if (rc) return rc;
-  for (int64_t q = 0; q < n; ++q) {
-    const int i = local(q), stt = mp.status[i];
-    if (status) status[q] = stt;
-    if (stt == 0) continue;
-    // unresolved, or P(genotype) subnormal: the input genotype, as hmc_get_resolutions gives it, at probability 0
-    if (prob) prob[q] = 0.0;
-    if (hap)
-      for (int side = 0; side < 2; ++side)
-        for (int l = 0; l < L; ++l)
-          hap[((size_t)q * 2 + side) * L + l] = pan.symbol(l, pan.idx[((size_t)(i0 + i) * 2 + side) * L + l]);
-  }
-  return HMC_OK;
-}
-
-int Ctx::ranked_phasings(int64_t n, const int32_t *indiv, int k, int32_t *hap, double *prob, int32_t *count, int32_t *status) {
-  if (!have_estep) return fail(HMC_EARG, "ranked phasings need an E-step first (hmc_resolve_all)");
-  if (estep_gen != model_gen)
-    return fail(HMC_EARG, "ranked phasings: the model changed since the last E-step (hmc_resolve_all again)");
-  if (pan.amax > 44) return fail(HMC_EUNSUPPORTED, "ranked phasings with more than 44 alleles per locus");
-  if (k < 1 || k > RANK_K_MAX) return fail(HMC_EARG, "ranked phasings: k = %d is outside [1, %d]", k, RANK_K_MAX);
-  const int nl = nloc(), L = pan.L;
-  if (!indiv) n = nl;
-  if (n < 0) return fail(HMC_EARG, "ranked phasings: n = %lld is negative", (long long)n);
-  for (int64_t q = 0; indiv && q < n; ++q)
-    if (indiv[q] < i0 || indiv[q] >= i1)
-      return fail(HMC_EARG, "ranked phasings: entry %lld: individual %d is outside this rank's shard [%d, %d)", (long long)q,
-                  indiv[q], i0, i1);
-  rk_ms_struct = rk_ms_fb = rk_ms_sweep = 0;
-  rk_groups = rk_pruned = rk_built = rk_batches = 0;
-  if (n == 0) return HMC_OK;
-  auto local = [&](int64_t q) { return indiv ? indiv[q] - i0 : (int)q; };
-  rk.draws = k;
-  rk.hap = hap;
-  rk.prob = prob;
-  rk.row_off.assign((size_t)nl + 1, 0);
-  for (int64_t q = 0; q < n; ++q) ++rk.row_off[local(q) + 1];
-  for (int i = 0; i < nl; ++i) rk.row_off[i + 1] += rk.row_off[i];
-  rk.rows.assign((size_t)n, 0);
-  {
-    std::vector<int64_t> at(rk.row_off.begin(), rk.row_off.end() - 1);
-    for (int64_t q = 0; q < n; ++q) rk.rows[at[local(q)]++] = q;
-  }
-  rk.status.assign(nl, 1);
-  rk_count.assign(nl, 0);
-  hipError_t er;
-  if ((er = d_xstatus.ensure(nl)) || (er = d_xre.ensure(nl)) || (er = d_xfmax.ensure(nl))) return hipfail(er, "ranked phasings");
-  // the pass counts in the genotype posteriors' fields: theirs are put back
-  const double g_struct = xp_ms_struct, g_fb = xp_ms_fb, g_sites = xp_ms_sites;
-  const int g_groups = xp_groups, g_pruned = xp_pruned;
-  std::vector<char> asked(nl, 0);  // the passes run over the individuals asked for, not the whole shard
-  for (int i = 0; i < nl; ++i) asked[i] = rk.row_off[i + 1] > rk.row_off[i];
-  const int rc = xp_pass(XP_RANK, "ranked phasings", &asked);
-  rk_ms_struct = xp_ms_struct;
-  rk_ms_fb = xp_ms_fb;
-  rk_ms_sweep = xp_ms_sites;
-  rk_groups = xp_groups;
-  rk_pruned = xp_pruned;
-  rk_built = rank_width(k);
-  xp_ms_struct = g_struct;
-  xp_ms_fb = g_fb;
-  xp_ms_sites = g_sites;
-  xp_groups = g_groups;
-  xp_pruned = g_pruned;
-  rk.hap = nullptr;
-  rk.prob = nullptr;
-  if (rc) return rc;
-  for (int64_t q = 0; q < n; ++q) {
-    const int i = local(q), stt = rk.status[i], cnt = stt == 0 ? rk_count[i] : 0;
-    if (status) status[q] = stt;
-    if (count) count[q] = cnt;
-    // rows past the count (all of them for an unresolved individual or a subnormal P(genotype)): the input
-    // genotype, as hmc_get_resolutions gives it, at probability 0
-    for (int r = cnt; r < k; ++r) {
-      if (prob) prob[(size_t)q * k + r] = 0.0;
-      if (hap)
-        for (int side = 0; side < 2; ++side)
-          for (int l = 0; l < L; ++l)
-            hap[(((size_t)q * k + r) * 2 + side) * L + l] = pan.symbol(l, pan.idx[((size_t)(i0 + i) * 2 + side) * L + l]);
-    }
-  }
-  return HMC_OK;
-}
-
-int Ctx::genotype_likelihoods(int64_t n, const int32_t *indiv, double *mantissa, int32_t *exponent, int32_t *status) {
-  if (!have_estep) return fail(HMC_EARG, "genotype likelihoods need an E-step first (hmc_resolve_all)");
-  if (estep_gen != model_gen)
-    return fail(HMC_EARG, "genotype likelihoods: the model changed since the last E-step (hmc_resolve_all again)");
-  if (pan.amax > 44) return fail(HMC_EUNSUPPORTED, "genotype likelihoods with more than 44 alleles per locus");
-  const int nl = nloc();
-  if (!indiv) n = nl;
-  if (n < 0) return fail(HMC_EARG, "genotype likelihoods: n = %lld is negative", (long long)n);
-  for (int64_t q = 0; indiv && q < n; ++q)
-    if (indiv[q] < i0 || indiv[q] >= i1)
-      return fail(HMC_EARG, "genotype likelihoods: entry %lld: individual %d is outside this rank's shard [%d, %d)",
-                  (long long)q, indiv[q], i0, i1);
-  lk_ms_struct = lk_ms_fb = 0;
-  lk_groups = 0;
-  if (n == 0) return HMC_OK;
-  auto local = [&](int64_t q) { return indiv ? indiv[q] - i0 : (int)q; };
-  lk.mantissa.assign(nl, 0.0);
-  lk.exponent.assign(nl, 0);
-  lk.status.assign(nl, 1);
-  hipError_t er;
-  if ((er = d_xstatus.ensure(nl)) || (er = d_xre.ensure(nl)) || (er = d_xfmax.ensure(nl))) return hipfail(er, "genotype likelihoods");
-  // the pass counts in the genotype posteriors' fields: theirs are put back
-  const double g_struct = xp_ms_struct, g_fb = xp_ms_fb, g_sites = xp_ms_sites;
-  const int g_groups = xp_groups, g_pruned = xp_pruned;
-  std::vector<char> asked(nl, 0);  // the passes run over the individuals asked for, not the whole shard
-  for (int64_t q = 0; q < n; ++q) asked[local(q)] = 1;
-  const int rc = xp_pass(XP_LIK, "genotype likelihoods", &asked);
-  lk_ms_struct = xp_ms_struct;
-  lk_ms_fb = xp_ms_fb;
-  lk_groups = xp_groups;
-  xp_ms_struct = g_struct;
-  xp_ms_fb = g_fb;
-  xp_ms_sites = g_sites;
-  xp_groups = g_groups;
-  xp_pruned = g_pruned;
-  if (rc) return rc;
-  for (int64_t q = 0; q < n; ++q) {
-    const int i = local(q);
-    if (mantissa) mantissa[q] = lk.mantissa[i];
-    if (exponent) exponent[q] = lk.exponent[i];
-    if (status) status[q] = lk.status[i];
-  }
-  return HMC_OK;
-}
-
-int Ctx::site_group(const ExactArgs &x, int k, int dev_cu) {
-  SiteArgs s;
-  s.site_off = d_site_off.p;
-  s.site_locus = d_site_locus.p;
-  s.post = d_site_post.p;
-  s.site_status = d_site_status.p;
-  s.n_pairs = pan.amax * (pan.amax + 1) / 2;
-  hipError_t e;
-  hipEventRecord(ev[0], st);
-  if ((e = launch_exact_site_posteriors(x, s, std::max(1, std::min(k, dev_cu * 8)), st))) return hipfail(e, "exact_site_posteriors");
-  hipEventRecord(ev[1], st);
-  if ((e = sync_st())) return hipfail(e, "exact_site_posteriors");
-  float ms = 0;
-  hipEventElapsedTime(&ms, ev[0], ev[1]);
-  xp_ms_sites += ms;
-  return HMC_OK;
-}
-
-void Ctx::site_list(SiteList &sl) const {
-  std::vector<unsigned long long> &off = sl.off;
-  std::vector<int32_t> &locus = sl.locus;
-  const int n = nloc(), L = pan.L;
-  off.assign((size_t)n + 1, 0);
-  locus.clear();
-  for (int i = 0; i < n; ++i) {
-    const uint8_t *g0 = pan.idx.data() + ((size_t)(i0 + i) * 2) * L, *g1 = g0 + L;
-    for (int k = 0; k < L; ++k)
-      if (g0[k] == MISSING || g1[k] == MISSING) locus.push_back(k);
-    off[i + 1] = locus.size();
-  }
-}
-
-int Ctx::xp_pass(XpMode mode, const char *what, const std::vector<char> *only) {
-  hipError_t er;
-  // What the exact-mode structure pass shares with the E-step and a later call
-  // can see is put back afterwards: the last E-step's pass times and counts,
-  // its per-individual status (hmc_get_estep), the frontier statistic and the
-  // structure stamps, and the capacities a restart may have grown.  The stores
-  // (records, traces) are dead between an E-step and the next M- or E-step.
-  const double s1_0 = ms_s1, fb_0 = ms_fb;
-  const int passes_0 = n_struct_passes, pruned_0 = exact_pruned, fcap_0 = fcap, ccap_0 = ccap_mult;
-  const uint64_t rec_words_0 = rec_words;
-  const std::vector<int32_t> status_0 = h_status;
-  uint32_t maxst_0 = 0;
-  unsigned long long stamps_0[20] = {};
-  if ((er = hipMemcpyAsync(&maxst_0, d_maxst.p, 4, hipMemcpyDeviceToHost, st)) ||
-      (er = hipMemcpyAsync(stamps_0, d_stamps.p + 20, sizeof stamps_0, hipMemcpyDeviceToHost, st)) || (er = sync_st()))
-    return hipfail(er, what);
-  const int n = nloc();
-  std::vector<int32_t> order;
-  for (int q = 0; q < n; ++q)
-    if (!only || (*only)[q]) order.push_back(q);
-  std::stable_sort(order.begin(), order.end(), [&](int x, int y) { return h_cost[x] > h_cost[y]; });
-  // The records of a cached exact M-step group are overwritten here, and the
-  // posteriors' own group must never be taken for one: no reuse on either side.
-  xc_reuse = false;
-  xp_mode = mode;
-  exact_pruned = 0;
-  ms_s1 = ms_fb = 0;
-  int rc;
-  while (true) {  // a capacity overflow restarts the pass; every site is written again
-    xc_groups = 0;
-    xp_ms_fb = xp_ms_sites = 0;
-    if (mode == XP_SWITCH) sw_spilled = 0;
-    if (mode == XP_PAIR) pr_spilled = 0;
-    if (mode == XP_DOSE) ds_spilled = 0;
-    rc = estep_split(order, true);
-    if (rc != ESTEP_RESTART) break;
-  }
-  xp_mode = XP_OFF;
-  xc_reuse = false;
-  xp_ms_struct = ms_s1 + ms_fb;  // (ms_fb: the pruned structure re-runs of underflowing individuals)
-  xp_groups = xc_groups;
-  xp_pruned = exact_pruned;
-  ms_s1 = s1_0;
-  ms_fb = fb_0;
-  n_struct_passes = passes_0;
-  exact_pruned = pruned_0;
-  fcap = fcap_0;
-  ccap_mult = ccap_0;
-  rec_words = rec_words_0;
-  h_status = status_0;
-  if ((er = hipMemcpyAsync(d_maxst.p, &maxst_0, 4, hipMemcpyHostToDevice, st)) ||
-      (er = hipMemcpyAsync(d_stamps.p + 20, stamps_0, sizeof stamps_0, hipMemcpyHostToDevice, st)) || (er = sync_st()))
-    return rc ? rc : hipfail(er, what);
-  return rc;
-}
-
-int Ctx::site_posteriors(int32_t *indiv, int32_t *locus, int32_t *status, double *post, const SiteList *pre) {
-  if (!have_estep) return fail(HMC_EARG, "genotype posteriors need an E-step first (hmc_resolve_all)");
-  // P(genotype) of the last E-step is the divisor: the table must still be the one it ran on
-  if (estep_gen != model_gen)
-    return fail(HMC_EARG, "genotype posteriors: the model changed since the last E-step (hmc_resolve_all again)");
-  if (pan.amax > 44)  // the records pack a locus's allele pairs (amax (amax + 1) / 2) in 10 bits
-    return fail(HMC_EUNSUPPORTED, "genotype posteriors with more than 44 alleles per locus");
-  const int n = nloc(), NP = pan.amax * (pan.amax + 1) / 2;
-  SiteList own;
-  if (!pre) site_list(own);
-  const std::vector<unsigned long long> &off = pre ? pre->off : own.off;
-  const std::vector<int32_t> &loc = pre ? pre->locus : own.locus;
-  const size_t ns = loc.size();
-  n_sites_last = ns;
-  xp_ms_struct = xp_ms_fb = xp_ms_sites = 0;
-  xp_groups = xp_pruned = 0;
-  if (indiv)
-    for (int i = 0; i < n; ++i)
-      for (unsigned long long q = off[i]; q < off[i + 1]; ++q) indiv[q] = i0 + i;
-  if (locus && ns) std::copy(loc.begin(), loc.end(), locus);
-  if (ns == 0) return HMC_OK;
-  hipError_t er;
-  if ((er = d_site_off.ensure((size_t)n + 1)) || (er = d_site_locus.ensure(ns)) || (er = d_site_status.ensure(ns)) ||
-      (er = d_site_post.ensure(ns * NP)) || (er = d_xstatus.ensure(n)) || (er = d_xre.ensure(n)) || (er = d_xfmax.ensure(n)) ||
-      (er = hipMemcpyAsync(d_site_off.p, off.data(), ((size_t)n + 1) * 8, hipMemcpyHostToDevice, st)) ||
-      (er = hipMemcpyAsync(d_site_locus.p, loc.data(), ns * 4, hipMemcpyHostToDevice, st)) ||
-      (er = hipMemsetAsync(d_site_post.p, 0, ns * NP * 8, st)) || (er = hipMemsetAsync(d_site_status.p, 0, ns * 4, st)))
-    return hipfail(er, "posteriors");
-  const int rc = xp_pass(XP_GENOTYPE, "posteriors");
-  if (rc) return rc;
-  if ((status && (er = hipMemcpyAsync(status, d_site_status.p, ns * 4, hipMemcpyDeviceToHost, st))) ||
-      (post && (er = hipMemcpyAsync(post, d_site_post.p, ns * NP * 8, hipMemcpyDeviceToHost, st))) || (er = sync_st()))
-    return hipfail(er, "posteriors");
-  return HMC_OK;
 }
 
 int Ctx::exact_walk_group(ExactArgs &x, int k, int dev_cu) {

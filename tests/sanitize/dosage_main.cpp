@@ -1,7 +1,8 @@
 // dosage_main.cpp — host sanitizer program for the GPU-free host code of
 // hmc_haplotype_dosages: the plan builder (hmc_amd/csrc/dosage_plan.hpp: slot
-// assignment, event order) and hmc_resolve's haplotype-list parser
-// (tools/hmc_hapfile.hpp).  Built with -fsanitize=address,undefined by
+// assignment, event order), hmc_resolve's haplotype-list parser
+// (tools/hmc_hapfile.hpp) and the queries' map between caller rows and shard
+// individuals (hmc_amd/csrc/query_rows.hpp).  Built with -fsanitize=address,undefined by
 // tests/test_dosage_host.py; every check aborts with a message.
 #include <cstdio>
 #include <cstdlib>
@@ -11,6 +12,7 @@
 #include <vector>
 
 #include "../../hmc_amd/csrc/dosage_plan.hpp"
+#include "../../hmc_amd/csrc/query_rows.hpp"
 #include "../../tools/hmc_hapfile.hpp"
 
 #define CHECK(c)                                                      \
@@ -138,9 +140,58 @@ static void hapfiles() {
   CHECK(parse("x 0 99999999999\n", "MM", o, err) == 1);
 }
 
+// One map: every caller row exactly once, under the individual it asks for; asked exactly where there are rows.
+static void check_rows(int64_t n, const int32_t *list, int i0, int i1) {
+  hmc::QueryRows r;
+  CHECK(r.build(n, list, i0, i1) == -1);
+  const int nl = i1 - i0;
+  CHECK(r.size() == n && (int)r.asked.size() == nl && (int)r.status.size() == nl && (int)r.row_off.size() == nl + 1);
+  std::vector<int> seen((size_t)n, 0);
+  for (int i = 0; i < nl; ++i) {
+    CHECK(r.begin(i) <= r.end(i) && r.status[(size_t)i] == 1);
+    CHECK((r.asked[(size_t)i] != 0) == (r.end(i) > r.begin(i)));
+    for (int64_t w = r.begin(i); w < r.end(i); ++w) {
+      const int64_t q = r.rows[(size_t)w];
+      CHECK(q >= 0 && q < n && !seen[(size_t)q]++);
+      CHECK(r.local(q) == i && (list ? list[q] : i0 + (int)q) == i0 + i);
+      CHECK(w == r.begin(i) || r.rows[(size_t)w - 1] < q);  // ascending: the first row is the caller's first
+    }
+  }
+  CHECK(r.begin(0) == 0 && r.end(nl - 1) == n);
+  for (int64_t q = 0; q < n; ++q) CHECK(seen[(size_t)q] == 1);
+}
+
+static void query_rows() {
+  std::mt19937 rng(20262);
+  for (int it = 0; it < 400; ++it) {
+    const int i0 = it % 3 == 0 ? 0 : (int)(rng() % 50), nl = 1 + (int)(rng() % 30), i1 = i0 + nl;
+    check_rows(nl, nullptr, i0, i1);  // the whole shard
+    const int64_t n = (int64_t)(rng() % 80);
+    std::vector<int32_t> list((size_t)n);
+    const int narrow = 1 + (int)(rng() % (unsigned)nl);  // few distinct individuals: repeats
+    for (auto &v : list) v = i0 + (int)(rng() % (unsigned)(it % 2 ? narrow : nl));
+    check_rows(n, list.data(), i0, i1);
+    check_rows(0, list.data(), i0, i1);  // an empty list
+    // an entry outside the shard, below or above it, is reported with its position; at 0 and at 1 every time
+    for (int64_t at : {(int64_t)0, (int64_t)1, n ? (int64_t)(rng() % (uint64_t)n) : (int64_t)0}) {
+      if (at >= n) continue;
+      std::vector<int32_t> bad = list;
+      bad[(size_t)at] = rng() % 2 ? i0 - 1 : i1;
+      hmc::QueryRows r;
+      CHECK(r.build(n, bad.data(), i0, i1) == at);
+      bad[(size_t)n - 1] = i1 + 7;  // a second one later: the first is named
+      CHECK(r.build(n, bad.data(), i0, i1) == at);
+    }
+  }
+  const std::vector<int32_t> two{9, 3};
+  hmc::QueryRows r;
+  CHECK(r.build(2, two.data(), 4, 9) == 0 && r.build(2, two.data(), 5, 10) == 1 && r.build(2, two.data(), 3, 10) == -1);
+}
+
 int main() {
   plans();
   hapfiles();
+  query_rows();
   printf("sanitized dosage host checks ok\n");
   return 0;
 }
