@@ -101,6 +101,15 @@ _SIGS = [
     ("hmc_map_phase", _i, [_vp, C.c_int64, _P(C.c_int32), _P(C.c_int32), _P(_d), _P(C.c_int32)]),
     ("hmc_last_map_stats", _i, [_vp, _P(_d), _P(_d), _P(_d), _P(_i), _P(_i)]),
     ("hmc_write_map_phase", _i, [_vp, _cp]),
+    ("hmc_map_phase_given", _i, [_vp, C.c_int64, _P(C.c_int32), C.c_int64, _P(C.c_int32), _P(C.c_int32), _P(C.c_int32),
+                                 _P(C.c_int32), _P(C.c_int32), _P(_d), _P(_d), _P(C.c_int32)]),
+    ("hmc_last_given_stats", _i, [_vp, _P(_d), _P(_d), _P(_d), _P(_i), _P(_i), _P(_i)]),
+    ("hmc_set_given_tuning", _i, [_vp, _i, _i]),
+    ("hmc_write_map_phase_given", _i, [_vp, _cp, C.c_int64, _P(C.c_int32), _P(C.c_int32), _P(C.c_int32), _P(C.c_int32)]),
+    ("hmc_read_evidence", _i, [_vp, _cp, _P(C.c_int64), _P(C.c_int32), _P(C.c_int32), _P(C.c_int32), _P(C.c_int32),
+                               C.c_int64]),
+    ("hmc_test_evidence_plan", _i, [_i, _i, _P(C.c_int32), C.c_int64, _P(C.c_int32), _P(C.c_int32), _P(C.c_int32),
+                                    _P(C.c_int32), C.c_char_p, _i, _P(C.c_int64), _P(_i), _P(C.c_int32), C.c_int64]),
     ("hmc_ranked_phasings", _i, [_vp, C.c_int64, _P(C.c_int32), _i, _P(C.c_int32), _P(_d), _P(C.c_int32), _P(C.c_int32)]),
     ("hmc_last_ranked_stats", _i, [_vp, _P(_d), _P(_d), _P(_d), _P(_i), _P(_i), _P(_i)]),
     ("hmc_set_ranked_tuning", _i, [_vp, _u64]),

@@ -8,6 +8,8 @@
 //   PatternManager::findPatternByFreq + initialize            -> Ctx::mine (mstep.hip)
 //   HaploModel::resolveAll        HaploModel.cpp:79-115      -> Ctx::estep (estep.hip)
 //   HaploModel::run               HaploModel.cpp:117-155     -> Ctx::run
+#include <fstream>
+
 #include "ctx.hpp"
 #include "philox.hpp"
 
@@ -1051,6 +1053,67 @@ int hmc_last_map_stats(const hmc_ctx *h, double *structure_ms, double *fb_ms, do
   return query_stats(h, Ctx::XP_MAP, structure_ms, fb_ms, sweep_ms, groups, n_pruned);
 }
 
+int hmc_map_phase_given(hmc_ctx *h, int64_t n, const int32_t *indiv, int64_t n_ev, const int32_t *ev_indiv, const int32_t *ev_locus,
+                        const int32_t *ev_set, const int32_t *ev_first, int32_t *hap, double *prob, double *evidence,
+                        int32_t *status) {
+  if (!h) return HMC_EARG;
+  Ctx &c = h->c;
+  if (!c.have_panel) return c.fail(HMC_EARG, "no panel loaded");
+  return c.map_phase_given(n, indiv, n_ev, ev_indiv, ev_locus, ev_set, ev_first, hap, prob, evidence, status);
+}
+
+int hmc_last_given_stats(const hmc_ctx *h, double *structure_ms, double *fb_ms, double *sweep_ms, int *groups, int *n_pruned,
+                         int *n_constrained) {
+  if (int rc = query_stats(h, Ctx::XP_GIVEN, structure_ms, fb_ms, sweep_ms, groups, n_pruned)) return rc;
+  if (n_constrained) *n_constrained = h->c.qstats[Ctx::XP_GIVEN].constrained;
+  return HMC_OK;
+}
+
+// Test seam of hmc_map_phase_given (not in the public header; results do not
+// depend on it): the block size (64, 128, 192 or 256) and the grid (0:
+// automatic) of exact_map_phase_given.
+int hmc_set_given_tuning(hmc_ctx *h, int block, int grid) {
+  if (!h) return HMC_EARG;
+  if (block < 64 || block > 256 || block % 64 || grid < 0 || grid > 65535)
+    return h->c.fail(HMC_EARG, "given tuning: block %d, grid %d (block 64 .. 256 in steps of 64, grid 0 .. 65535)", block, grid);
+  h->c.gv_block = block;
+  h->c.gv_grid = grid;
+  return HMC_OK;
+}
+
+// The host plan of hmc_map_phase_given without a context or a device (test
+// seam, not in the public header): the panel as alleles[N][2][L] symbols (-1
+// missing), every individual asked for.  0, HMC_EARG or HMC_EUNSUPPORTED with
+// the message in msg[msg_cap]; on success the number of events kept and of
+// individuals with any, and the events (locus, flags | allele rank << 8)
+// individual-major when ev_out[2 * ev_cap] holds them.
+int hmc_test_evidence_plan(int N, int L, const int32_t *alleles, int64_t n_ev, const int32_t *ev_indiv, const int32_t *ev_locus,
+                           const int32_t *ev_set, const int32_t *ev_first, char *msg, int msg_cap, int64_t *n_events,
+                           int *n_constrained, int32_t *ev_out, int64_t ev_cap) {
+  if (N < 0 || L < 0 || (N > 0 && L > 0 && !alleles) || n_ev < 0 || (n_ev > 0 && (!ev_indiv || !ev_locus || !ev_set || !ev_first)))
+    return HMC_EARG;
+  hmc::EvidencePlan pl;
+  std::string m;
+  auto rank_of = [&](int k, int32_t a) {  // the symbol's rank among the locus's distinct symbols (Panel::index_of)
+    std::vector<int32_t> seen;
+    for (size_t q = 0; q < (size_t)N * 2; ++q) {
+      const int32_t x = alleles[q * L + k];
+      if (x >= 0 && x < a && std::find(seen.begin(), seen.end(), x) == seen.end()) seen.push_back(x);
+    }
+    return (int)seen.size();
+  };
+  const int er = hmc::evidence_plan(N, L, alleles, 0, N, nullptr, n_ev, ev_indiv, ev_locus, ev_set, ev_first, rank_of, pl, m);
+  if (msg && msg_cap > 0) snprintf(msg, (size_t)msg_cap, "%s", m.c_str());
+  if (er) return er == hmc::EVP_EARG ? HMC_EARG : HMC_EUNSUPPORTED;
+  if (n_events) *n_events = (int64_t)pl.ev.size();
+  if (n_constrained) *n_constrained = pl.n_constrained;
+  for (size_t e = 0; ev_out && e < pl.ev.size() && (int64_t)e < ev_cap; ++e) {
+    ev_out[2 * e] = pl.ev[e].locus;
+    ev_out[2 * e + 1] = pl.ev[e].code;
+  }
+  return HMC_OK;
+}
+
 int hmc_ranked_phasings(hmc_ctx *h, int64_t n, const int32_t *indiv, int k, int32_t *hap, double *prob, int32_t *count,
                         int32_t *status) {
   if (!h) return HMC_EARG;
@@ -1376,6 +1439,50 @@ int hmc_write_map_phase(hmc_ctx *h, const char *path) {
           fputc('\n', fp);
         }
       });
+}
+
+int hmc_write_map_phase_given(hmc_ctx *h, const char *path, int64_t n_ev, const int32_t *ev_indiv, const int32_t *ev_locus,
+                              const int32_t *ev_set, const int32_t *ev_first) {
+  if (!h || !path || !h->c.have_panel) return HMC_EARG;
+  Ctx &c = h->c;
+  const int L = c.pan.L;
+  const size_t per = (size_t)2 * L;
+  const int nb = batch_size(c, HAP_BATCH, per);
+  std::vector<int32_t> hap((size_t)nb * per), status(nb);
+  std::vector<double> prob(nb), evid(nb);
+  return write_batches(
+      c, path, nb, "Id\tStatus\tPosterior\tEvidence\n",
+      [&](int k, const int32_t *indiv) {
+        return c.map_phase_given(k, indiv, n_ev, ev_indiv, ev_locus, ev_set, ev_first, hap.data(), prob.data(), evid.data(),
+                                 status.data());
+      },
+      [&](FILE *fp, int i, const char *id) {
+        fprintf(fp, "%s\t%d\t%.17g\t%.17g\n", id, status[i], prob[i], evid[i]);
+        for (int side = 0; side < 2; ++side) {
+          spell_alleles(fp, c, hap.data() + ((size_t)i * 2 + side) * L, 0);
+          fputc('\n', fp);
+        }
+      });
+}
+
+int hmc_read_evidence(hmc_ctx *h, const char *path, int64_t *n_ev, int32_t *ev_indiv, int32_t *ev_locus, int32_t *ev_set,
+                      int32_t *ev_first, int64_t cap) {
+  if (!h || !path || !h->c.have_panel) return HMC_EARG;
+  Ctx &c = h->c;
+  std::ifstream in(path);
+  if (!in) return c.fail(HMC_EIO, "Can not open file %s!", path);
+  const hmc::FileData d = writer_meta(c);
+  hmc::EvidenceTable t;
+  std::string err;
+  if (hmc::parse_evidence(in, d.ids, d.names, c.pan.types, t, err)) return c.fail(HMC_EARG, "%s", err.c_str());
+  if (n_ev) *n_ev = (int64_t)t.indiv.size();
+  for (size_t e = 0; e < t.indiv.size() && (int64_t)e < cap; ++e) {
+    if (ev_indiv) ev_indiv[e] = t.indiv[e];
+    if (ev_locus) ev_locus[e] = t.locus[e];
+    if (ev_set) ev_set[e] = t.set[e];
+    if (ev_first) ev_first[e] = t.first[e];
+  }
+  return HMC_OK;
 }
 
 int hmc_write_ranked_phasings(hmc_ctx *h, const char *path, int k) {

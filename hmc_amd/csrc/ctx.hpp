@@ -811,20 +811,20 @@ struct Ctx {
   void site_list(SiteList &sl) const;
   int site_group(const ExactArgs &x, int k, int dev_cu);
   // what the exact group runs after exact_fb in place of the trie walk
-  enum XpMode { XP_OFF = 0, XP_GENOTYPE = 1, XP_SWITCH = 2, XP_PAIR = 3, XP_DRAW = 4, XP_LIK = 5, XP_DOSE = 6, XP_MAP = 7, XP_RANK = 8 };
+  enum XpMode { XP_OFF = 0, XP_GENOTYPE = 1, XP_SWITCH = 2, XP_PAIR = 3, XP_DRAW = 4, XP_LIK = 5, XP_DOSE = 6, XP_MAP = 7, XP_RANK = 8, XP_GIVEN = 9 };
   XpMode xp_mode = XP_OFF;
-  // What the eight queries share (ctx_query.cpp).  Of a kind's last call:
+  // What the nine queries share (ctx_query.cpp).  Of a kind's last call:
   // device ms of the structure passes, of exact_fb and of the kind's own
   // kernels (draws_to_symbols included); groups; individuals on pruned
   // records; individuals whose largest record exceeded the tier; the NS used;
   // rounds (pairs: most of any individual, dosages: sweeps the plan takes); the
-  // list width KL of the ranked kernel that ran; launches.  A kind leaves at
-  // zero what it does not use.  The running pass writes its own kind's record.
+  // list width KL of the ranked kernel that ran; launches; individuals that
+  // ran exact_map_phase_given.  A kind leaves at zero what it does not use.  The running pass writes its own kind's record.
   struct QueryStats {
     double ms_struct = 0, ms_fb = 0, ms_sweep = 0;
-    int groups = 0, pruned = 0, spilled = 0, slots = 0, rounds = 0, built = 0, batches = 0;
+    int groups = 0, pruned = 0, spilled = 0, slots = 0, rounds = 0, built = 0, batches = 0, constrained = 0;
   };
-  QueryStats qstats[XP_RANK + 1];  // by XpMode
+  QueryStats qstats[XP_GIVEN + 1];  // by XpMode
   // HMC_OK, or the error of a query that cannot run: no E-step yet, a model
   // changed since it, more than 44 alleles per locus
   int query_ready(XpMode kind);
@@ -967,6 +967,27 @@ struct Ctx {
   // Rows are the caller's, batches and device buffers the draws' with one draw.
   int map_phase(int64_t n, const int32_t *indiv, int32_t *hap, double *prob, int32_t *status);
   int map_group(const ExactArgs &x, const int32_t *ids, int k, int dev_cu);
+  // (sel: the group's asked individuals that take exact_map_phase)
+  int map_sel(const ExactArgs &x, const std::vector<int32_t> &sel, int dev_cu);
+  // MAP phasing given phase sets (hmc_map_phase_given): hmc_map_phase over the
+  // pairs consistent with caller-given evidence, and P(evidence | genotype).
+  // The plan (evidence_plan.hpp) is built once per call for the individuals
+  // asked for and goes to the device as one offsets and one event array.  Per
+  // group (XP_GIVEN) the individuals without events take exact_map_phase itself
+  // (map_sel; evidence exactly 1.0), the others exact_map_phase_given, which
+  // sweeps the same x-store slots: batches and buffers are map_group's.
+  int map_phase_given(int64_t n, const int32_t *indiv, int64_t n_ev, const int32_t *ev_indiv, const int32_t *ev_locus,
+                      const int32_t *ev_set, const int32_t *ev_first, int32_t *hap, double *prob, double *evidence,
+                      int32_t *status);
+  int given_group(const ExactArgs &x, const int32_t *ids, int k, int dev_cu);
+  struct GivenCall {  // the running call
+    EvidencePlan plan;
+    double *evidence = nullptr;
+  } gv;
+  DevBuf<unsigned long long> d_gv_off;
+  DevBuf<GivenEvent> d_gv_ev;
+  DevBuf<double> d_gv_evid;
+  int gv_block = 256, gv_grid = 0;  // hmc_set_given_tuning (test seam): the new kernel's block size and grid (0: automatic)
   // Ranked phasings (hmc_ranked_phasings): the k most probable haplotype
   // pairs per asked individual, each once, with their exact posteriors;
   // exact_ranked_phasings per group (XP_RANK) after exact_fb's forward-only

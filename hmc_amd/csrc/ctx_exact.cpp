@@ -200,7 +200,8 @@ int Ctx::exact_group(const int32_t *ids, int k, const std::function<int(std::vec
   x.head_al = d_head_al.p;
   x.acc_freq = d_xacc.p;
   x.acc_prefix = d_xacc.p + xacc_nc;
-  x.forward_only = (xp_mode == XP_DRAW && dr_forward_only) || xp_mode == XP_LIK || xp_mode == XP_MAP || xp_mode == XP_RANK;
+  x.forward_only = (xp_mode == XP_DRAW && dr_forward_only) || xp_mode == XP_LIK || xp_mode == XP_MAP || xp_mode == XP_RANK ||
+                   xp_mode == XP_GIVEN;
   // extended range: the posterior calls when asked for, the likelihoods always, the exact M-step never
   x.extended = xp_mode == XP_LIK || (xp_mode != XP_OFF && xp_extended);
   if (x.extended) {
@@ -264,6 +265,7 @@ int Ctx::exact_group(const int32_t *ids, int k, const std::function<int(std::vec
   if (xp_mode == XP_DOSE) return dosage_group(x, ids, fm, k, dev_cu);
   if (xp_mode == XP_MAP) return map_group(x, ids, k, dev_cu);
   if (xp_mode == XP_RANK) return ranked_group(x, ids, k, dev_cu);
+  if (xp_mode == XP_GIVEN) return given_group(x, ids, k, dev_cu);
   if (xp_mode == XP_LIK) {  // the scaled totals of the group's individuals: nothing runs after exact_fb
     std::vector<double> tot(n);
     std::vector<int32_t> ex(n);

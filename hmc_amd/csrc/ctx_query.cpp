@@ -1,5 +1,5 @@
 // ctx_query.cpp — Ctx members: the posterior queries on the exact lattice (genotype, switch and pair posteriors,
-// posterior draws, genotype likelihoods, haplotype dosages, MAP and ranked phasings).  Each runs the shard through
+// posterior draws, genotype likelihoods, haplotype dosages, MAP and ranked phasings, MAP phasing given phase sets).  Each runs the shard through
 // estep_split(order, true) like a round of the exact M-step (xp_pass) with a kernel of its own per group in place of
 // the trie walk (exact_group, ctx_exact.cpp).  The kernels differ; the host code around them is written once here.
 #include "ctx.hpp"
@@ -15,11 +15,12 @@ static const char *const QUERY_NOUN[] = {"",
                                          "genotype likelihoods",
                                          "haplotype dosages",
                                          "MAP phasing",
-                                         "ranked phasings"};
+                                         "ranked phasings",
+                                         "MAP phasing given evidence"};
 
 int Ctx::query_ready(XpMode kind) {
   const char *noun = QUERY_NOUN[kind];
-  if (!have_estep) return fail(HMC_EARG, "%s need%s an E-step first (hmc_resolve_all)", noun, kind == XP_MAP ? "s" : "");
+  if (!have_estep) return fail(HMC_EARG, "%s need%s an E-step first (hmc_resolve_all)", noun, kind == XP_MAP || kind == XP_GIVEN ? "s" : "");
   // P(genotype) of the last E-step is the divisor: the table must still be the one it ran on
   if (estep_gen != model_gen)
     return fail(HMC_EARG, "%s: the model changed since the last E-step (hmc_resolve_all again)", noun);
@@ -470,11 +471,12 @@ static void copy_staged(int u, int64_t row, int D, size_t per, const std::vector
   if (hap) std::copy(h_hap.begin() + (size_t)u * per, h_hap.begin() + (size_t)(u + 1) * per, hap + (size_t)row * per);
 }
 
-int Ctx::map_group(const ExactArgs &x, const int32_t *ids, int k, int dev_cu) {
+int Ctx::map_group(const ExactArgs &x, const int32_t *ids, int k, int dev_cu) { return map_sel(x, asked_in(ids, k), dev_cu); }
+
+int Ctx::map_sel(const ExactArgs &x, const std::vector<int32_t> &sel, int dev_cu) {
   const int L = pan.L, A = pan.amax;
   const size_t per = (size_t)2 * L;  // haplotype entries of one individual
   const size_t cap = std::max<size_t>(1, DRAW_OUT_BYTES / (8 + (dr.hap ? per * 5 : 0)));
-  const std::vector<int32_t> sel = asked_in(ids, k);
   std::vector<int32_t> h_hap;
   std::vector<double> h_prob;
   return query_batches(
@@ -510,8 +512,94 @@ int Ctx::map_group(const ExactArgs &x, const int32_t *ids, int k, int dev_cu) {
       },
       [&](int u, int64_t row, int64_t) {
         copy_staged(u, row, 1, per, h_prob, h_hap, dr.prob, dr.hap);
+        if (gv.evidence) gv.evidence[row] = 1.0;  // (hmc_map_phase_given: an individual without events)
         return hipSuccess;
       });
+}
+
+int Ctx::given_group(const ExactArgs &x, const int32_t *ids, int k, int dev_cu) {
+  const int L = pan.L, A = pan.amax;
+  const size_t per = (size_t)2 * L;
+  const size_t cap = std::max<size_t>(1, DRAW_OUT_BYTES / (16 + (dr.hap ? per * 5 : 0)));
+  std::vector<int32_t> plain, sel;  // the group's asked individuals without and with events
+  for (int32_t bi : asked_in(ids, k)) (gv.plan.off[(size_t)bi + 1] > gv.plan.off[(size_t)bi] ? sel : plain).push_back(bi);
+  if (int rc = map_sel(x, plain, dev_cu)) return rc;
+  qstats[XP_GIVEN].constrained += (int)sel.size();
+  std::vector<int32_t> h_hap;
+  std::vector<double> h_prob, h_evid;
+  return query_batches(
+      "exact_map_phase_given", x, sel, d_dr_order, d_dr_status,
+      [&](size_t pos, int &nb) {
+        nb = (int)std::min(cap, sel.size() - pos);
+        return HMC_OK;
+      },
+      [&](const ExactArgs &xb, size_t, int nb) {
+        const int grid = gv_grid > 0 ? gv_grid : std::max(1, std::min(nb, dev_cu * 8));
+        hipError_t e;
+        if ((e = d_dr_prob.ensure(nb)) || (e = d_gv_evid.ensure(nb)) || (dr.hap && (e = d_dr_al.ensure((size_t)nb * per))) ||
+            (dr.hap && (e = d_dr_hap.ensure((size_t)nb * per))) || (e = hipMemsetAsync(d_dr_prob.p, 0, (size_t)nb * 8, st)) ||
+            (e = hipMemsetAsync(d_gv_evid.p, 0, (size_t)nb * 8, st)) ||
+            (dr.hap && (e = hipMemsetAsync(d_dr_al.p, 0xFF, (size_t)nb * per, st))))
+          return hipfail(e, "exact_map_phase_given");
+        GivenArgs s;
+        s.ev_off = d_gv_off.p;
+        s.ev = d_gv_ev.p;
+        s.al = dr.hap ? d_dr_al.p : nullptr;
+        s.prob = d_dr_prob.p;
+        s.evidence = d_gv_evid.p;
+        s.status = d_dr_status.p;
+        if (int rc = timed_sweep("exact_map_phase_given", [&]() {
+              if ((e = launch_exact_map_phase_given(xb, s, grid, st, gv_block))) return hipfail(e, "exact_map_phase_given");
+              if (dr.hap && (e = launch_draws_to_symbols(d_dr_al.p, d_dr_sym.p, d_dr_hap.p, nb, L, 1, A, st)))
+                return hipfail(e, "draws_to_symbols");
+              return (int)HMC_OK;
+            }))
+          return rc;
+        h_prob.resize(nb);
+        h_evid.resize(nb);
+        h_hap.resize(dr.hap ? (size_t)nb * per : 0);
+        if ((e = hipMemcpyAsync(h_prob.data(), d_dr_prob.p, (size_t)nb * 8, hipMemcpyDeviceToHost, st)) ||
+            (e = hipMemcpyAsync(h_evid.data(), d_gv_evid.p, (size_t)nb * 8, hipMemcpyDeviceToHost, st)) ||
+            (dr.hap && (e = hipMemcpyAsync(h_hap.data(), d_dr_hap.p, (size_t)nb * per * 4, hipMemcpyDeviceToHost, st))))
+          return hipfail(e, "exact_map_phase_given");
+        return (int)HMC_OK;
+      },
+      [&](int u, int64_t row, int64_t) {
+        copy_staged(u, row, 1, per, h_prob, h_hap, dr.prob, dr.hap);
+        if (gv.evidence) gv.evidence[row] = h_evid[u];
+        return hipSuccess;
+      });
+}
+
+int Ctx::map_phase_given(int64_t n, const int32_t *indiv, int64_t n_ev, const int32_t *ev_indiv, const int32_t *ev_locus,
+                         const int32_t *ev_set, const int32_t *ev_first, int32_t *hap, double *prob, double *evidence,
+                         int32_t *status) {
+  int rc;
+  if ((rc = query_ready(XP_GIVEN))) return rc;
+  if (n_ev < 0 || (n_ev > 0 && (!ev_indiv || !ev_locus || !ev_set || !ev_first)))
+    return fail(HMC_EARG, "MAP phasing given evidence: n_ev = %lld with an evidence array missing", (long long)n_ev);
+  if ((rc = query_rows(XP_GIVEN, n, indiv))) return rc;
+  n = qr.size();
+  std::string msg;
+  const int er = evidence_plan(pan.N, pan.L, pan.al.data(), i0, i1, qr.asked.data(), n_ev, ev_indiv, ev_locus, ev_set, ev_first,
+                               [&](int k, int32_t a) { return pan.index_of(k, a); }, gv.plan, msg);
+  if (er) return fail(er == EVP_EARG ? HMC_EARG : HMC_EUNSUPPORTED, "MAP phasing given evidence: %s", msg.c_str());
+  if (n > 0) {
+    const std::vector<GivenEvent> &ev = gv.plan.ev;
+    hipError_t e;
+    if ((e = d_gv_off.ensure(gv.plan.off.size())) || (e = d_gv_ev.ensure(std::max<size_t>(1, ev.size()))) ||
+        (e = hipMemcpyAsync(d_gv_off.p, gv.plan.off.data(), gv.plan.off.size() * 8, hipMemcpyHostToDevice, st)) ||
+        (!ev.empty() && (e = hipMemcpyAsync(d_gv_ev.p, ev.data(), ev.size() * sizeof(GivenEvent), hipMemcpyHostToDevice, st))) ||
+        (e = sync_st()))
+      return hipfail(e, "MAP phasing given evidence");
+  }
+  gv.evidence = evidence;
+  rc = hap_query(XP_GIVEN, n, indiv, 1, 0, hap, prob, nullptr, status);
+  gv.evidence = nullptr;
+  if (rc) return rc;
+  for (int64_t q = 0; evidence && q < n; ++q)
+    if (qr.status[qr.local(q)] != 0) evidence[q] = 0.0;
+  return HMC_OK;
 }
 
 int Ctx::ranked_group(const ExactArgs &x, const int32_t *ids, int k, int dev_cu) {
@@ -849,7 +937,7 @@ int Ctx::xp_pass(XpMode mode, const char *what, const std::vector<char> *only) {
   while (true) {  // a capacity overflow restarts the pass; every site is written again
     xc_groups = 0;
     qs.ms_fb = qs.ms_sweep = 0;
-    qs.spilled = 0;
+    qs.spilled = qs.constrained = 0;
     rc = estep_split(order, true);
     if (rc != ESTEP_RESTART) break;
   }

@@ -2306,6 +2306,398 @@ hipError_t launch_exact_map_phase(const ExactArgs &a, const MapArgs &s, int grid
   return hipGetLastError();
 }
 
+// MAP phasing given phase sets (hmc_map_phase_given): exact_map_phase over the
+// pairs consistent with the individual's evidence, and P(evidence | genotype).
+// The host plan (evidence_plan.hpp) gives the constrained loci ascending, each
+// with the allele index on its set's first haplotype, a set's first locus
+// marked as anchor and its last as last; sets do not overlap.  The record of
+// locus k is k + 1, or head_len for k < head_len.
+// A set needs an orientation label c: its first haplotype lies on the state's
+// a side (c = 0) or b side (c = 1); a predecessor's label c arrives as
+// c ^ rev(r) (exact_haplotype_dosages' rule).  Every path through a set's first
+// locus is heterozygous from there on, so inside a span Vh is 0, and outside
+// any span there is no label: two values per state still hold everything.
+//   span record (from the record of a set's first locus to that of its last,
+//   when these differ): (V[0], V[1]) by label;
+//   plain record: (Vh, Vd) as map_sweep.
+// Max sweep, record j above the head, state t with alleles (xa, xb) of locus
+// j - 1, primes for the record below:
+//   anchor   m = max_r max(Vd'[p], 2 Vh'[p]) over a plain record below, max_r
+//            max(V'[0][p], V'[1][p]) over a span record below (adjacent sets);
+//            V[0] = tpv m if xa is the first allele, V[1] = tpv m if xb is, the
+//            other label 0;
+//   inside   V[c] = tpv max_r V'[c ^ rev(r)][p]; at a locus of the set a label
+//            whose side does not carry the first allele is stored as 0, at any
+//            other locus both labels pass;
+//   plain    map_sweep's recurrence; over a span record below it reads Vd' =
+//            max(V'[0], V'[1]) and Vh' = 0.
+// Head record: the constrained loci below head_len are matched from the states'
+// two head patterns (head_len = 1: from the state's alleles); a state that
+// fails a set wholly inside the head is 0, and when a set continues above the
+// head the head record is a span record with the state's value under the
+// label(s) that match.  Scaling and the regular range's second, rescaled sweep
+// as exact_map_phase.
+// Sum sweep: the same with ordered sums in place of maxima (contributions in
+// record order, the first assigns; two labels of one predecessor as V'[0] +
+// V'[1]) and one value per plain state, every record rescaled in both ranges.
+// The final record summed in state order from 0.0 (a span record: V[0][t] +
+// V[1][t] per state) is P(evidence and genotype): a heterozygous pair behind a
+// homozygous prefix is two mirror paths of half each, and both pass or both
+// fail every set, since a set constrains relative orientation only.  Divided by
+// the range's P(genotype) it is `evidence`; a sum of exactly 0 is status 3 and
+// no max sweep runs.
+// The sweeps leave each record's kind in its second spare word (bit 0: span
+// record, bit 1: inside, i.e. reads label by label) for the traceback, which is
+// exact_map_phase's: candidates of the final record by index 2 t + label (h = 0,
+// d = 1; on a span record the label is c), largest value, lowest index.  Going
+// down from state t with label l, contributions in record order, the first that
+// attains the maximum, 64 at a time under (value, lowest index):
+//   inside                  V'[l ^ rev(r)], the label becomes l ^ rev(r);
+//   over a span record      V'[0] and then V'[1] per contribution (index 2
+//   (anchor or plain d)     lane + c), the label becomes that c;
+//   anchor over plain, and  Vd' and then 2 Vh' per contribution, the label
+//   plain d at xa != xb     becomes d or h;
+//   otherwise               Vh' for h, Vd' for d.
+// A label stored as 0 is never chosen: only positive values are.
+template <bool SUM, bool SCALE>
+__device__ inline int given_sweep(const ExactArgs &a, const unsigned long long *roff, const unsigned long long *xo,
+                                  const GivenEvent *ev, int ne, int *flag, bool &top_labels) {
+  const int tid = threadIdx.x, NT = blockDim.x;
+  const int L = a.L, hl = a.head_len;
+  int ex = 0, Fp = 0, ec = 0;        // the cumulative exponent; the states of the record below; the next event
+  bool open = false, below = false;  // a set continues above this record; the record below is a span record (block-uniform)
+  {
+    const RecView R(a.rec + roff[hl], true);
+    double *v0 = (double *)(a.x + xo[hl]), *v1 = v0 + R.F;
+    while (ec < ne && ev[ec].locus < hl) ++ec;  // the head's events: [0, ec)
+    const int nh = ec;
+    open = nh > 0 && !(ev[nh - 1].code & GIVEN_EV_LAST);
+    const uint32_t *plo = R.cb + R.F + 1, *phi = plo + R.F;
+    double m = 0.0;
+    for (int t = tid; t < R.F; t += NT) {
+      const uint32_t hd = R.hdr[t];
+      const bool homo = (hd >> 24) & 1u;
+      bool ok = true, c0 = true, c1 = true;
+      for (int e = 0; e < nh; ++e) {
+        const int k = ev[e].locus, code = ev[e].code;
+        const uint32_t first = (uint32_t)(code >> 8);
+        uint32_t xa, xb;
+        if (hl == 1) {
+          xa = hd & 0xFFu;
+          xb = (hd >> 8) & 0xFFu;
+        } else {
+          xa = a.head_al[(size_t)plo[t] * hl + k];
+          xb = a.head_al[(size_t)phi[t] * hl + k];
+        }
+        if (code & GIVEN_EV_ANCHOR) c0 = c1 = true;
+        c0 = c0 && xa == first;
+        c1 = c1 && xb == first;
+        if (code & GIVEN_EV_LAST) ok = ok && (c0 || c1);
+      }
+      const double tpv = R.tpv[t], val = homo ? tpv : tpv * 2.0;
+      double o0, o1;
+      if (open) {
+        o0 = ok && c0 ? val : 0.0;
+        o1 = ok && c1 ? val : 0.0;
+      } else if (SUM) {
+        o0 = ok ? val : 0.0;
+        o1 = 0.0;
+      } else {
+        o0 = ok && homo ? val : 0.0;
+        o1 = ok && !homo ? val : 0.0;
+      }
+      v0[t] = o0;
+      v1[t] = o1;
+      if constexpr (SCALE) m = fmax(m, fmax(o0, o1));
+    }
+    if constexpr (SCALE) ex += rescale_record(v0, 2 * R.F, m);
+    else __syncthreads();
+    if (tid == 0) {
+      int32_t *sp = (int32_t *)(v0 + 2 * (size_t)R.F);
+      sp[0] = ex;
+      sp[1] = open ? 1 : 0;
+    }
+    Fp = R.F;
+    below = open;
+  }
+  for (int j = hl + 1; j <= L; ++j) {
+    const RecView R(a.rec + roff[j], false);
+    const double *p0 = (const double *)(a.x + xo[j - 1]), *p1 = p0 + Fp;
+    double *v0 = (double *)(a.x + xo[j]), *v1 = v0 + R.F;
+    const bool has = ec < ne && ev[ec].locus == j - 1;
+    const int code = has ? ev[ec].code : 0;
+    const uint32_t first = (uint32_t)(code >> 8);
+    const bool cont = open, labels = open || (code & GIVEN_EV_ANCHOR);
+    double m = 0.0;
+    for (int t = tid; t < R.F; t += NT) {
+      const uint32_t hd = R.hdr[t], xa = hd & 0xFFu, xb = (hd >> 8) & 0xFFu;
+      const uint32_t r0 = R.cb[t], r1 = R.cb[t + 1];
+      double a0 = 0.0, a1 = 0.0;
+      if (cont) {  // label by label
+        for (uint32_t r = r0; r < r1; ++r) {
+          const uint32_t w = R.ct[r], p = cw_state(w);
+          const bool rv = cw_rev(w);
+          const double s0 = rv ? p1[p] : p0[p], s1 = rv ? p0[p] : p1[p];
+          if constexpr (SUM) {
+            a0 = r == r0 ? s0 : a0 + s0;
+            a1 = r == r0 ? s1 : a1 + s1;
+          } else {
+            a0 = fmax(a0, s0);
+            a1 = fmax(a1, s1);
+          }
+        }
+      } else if (labels || SUM) {  // one value per predecessor: an anchor, or a plain record of the sum sweep
+        for (uint32_t r = r0; r < r1; ++r) {
+          const uint32_t p = cw_state(R.ct[r]);
+          if constexpr (SUM) {
+            const double sv = below ? p0[p] + p1[p] : p0[p];
+            a0 = r == r0 ? sv : a0 + sv;
+          } else {
+            a0 = fmax(a0, below ? fmax(p0[p], p1[p]) : fmax(p1[p], 2.0 * p0[p]));
+          }
+        }
+        a1 = a0;
+      } else {  // a plain record of the max sweep: map_sweep's recurrence
+        const bool homo = xa == xb;
+        for (uint32_t r = r0; r < r1; ++r) {
+          const uint32_t p = cw_state(R.ct[r]);
+          const double h = below ? 0.0 : p0[p], d = below ? fmax(p0[p], p1[p]) : p1[p];
+          if (homo) {
+            a0 = fmax(a0, h);
+            a1 = fmax(a1, d);
+          } else {
+            a1 = fmax(a1, fmax(d, 2.0 * h));
+          }
+        }
+      }
+      const double tpv = R.tpv[t];
+      const bool ok0 = labels ? !has || xa == first : true, ok1 = labels ? !has || xb == first : !SUM;
+      const double o0 = ok0 ? tpv * a0 : 0.0, o1 = ok1 ? tpv * a1 : 0.0;
+      v0[t] = o0;
+      v1[t] = o1;
+      if constexpr (SCALE) m = fmax(m, fmax(o0, o1));
+      else if ((ok0 && a0 > 0.0 && o0 < SITE_PG_MIN) || (ok1 && a1 > 0.0 && o1 < SITE_PG_MIN)) *flag = 1;
+    }
+    if constexpr (SCALE) ex += rescale_record(v0, 2 * R.F, m);
+    else __syncthreads();
+    if (tid == 0) {
+      int32_t *sp = (int32_t *)(v0 + 2 * (size_t)R.F);
+      sp[0] = ex;
+      sp[1] = (labels ? 1 : 0) | (cont ? 2 : 0);
+    }
+    Fp = R.F;
+    below = labels;
+    open = labels && !(code & GIVEN_EV_LAST);
+    if (has) ++ec;
+  }
+  top_labels = below;
+  return ex;
+}
+
+template <bool EXT>
+__global__ __launch_bounds__(256) void exact_map_phase_given(ExactArgs a, GivenArgs s) {
+  __shared__ double bv[4];
+  __shared__ unsigned bk[4];
+  __shared__ int flag;
+  __shared__ double s_tot;
+  const int tid = threadIdx.x, NT = blockDim.x, lane = tid & (WAVE - 1), wave = tid / WAVE, nw = NT / WAVE;
+  const int L = a.L, hl = a.head_len;
+  for (int q = blockIdx.x; q < a.n_order; q += gridDim.x) {  // block-uniform
+    const int bi = a.order[q];
+    const int st0 = a.status[bi];
+    const double pg = EXT ? a.xtot[bi] : a.gprob[bi];
+    const int pge = EXT ? -a.xtot_exp[bi] : 0;  // P(genotype) = pg 2^pge
+    const bool resolved = (st0 == EST_OK || st0 == EST_OK_PRUNED) && pg > 0.0 && !isinf(pg);
+    if (!resolved || (!EXT && pg < SITE_PG_MIN)) {  // as exact_map_phase: unresolved (1), P(genotype) subnormal (2)
+      if (tid == 0) s.status[q] = resolved ? 2 : 1;
+      continue;
+    }
+    const unsigned long long *roff = a.rec_off + (size_t)bi * (L + 1);
+    const unsigned long long *xo = a.x_off + (size_t)bi * (L + 1);
+    const GivenEvent *ev = s.ev + s.ev_off[bi];
+    const int ne = (int)(s.ev_off[bi + 1] - s.ev_off[bi]);
+    // the sums: P(evidence and genotype) = tot 2^-es
+    bool top = false;
+    const int es = given_sweep<true, true>(a, roff, xo, ev, ne, &flag, top);
+    if (tid == 0) {  // in state order from 0.0, as exact_fb sums its divisor
+      const int F = (int)a.rec[roff[L]];
+      const double *v = (const double *)(a.x + xo[L]);
+      double tot = 0.0;
+      for (int t = 0; t < F; ++t) tot += top ? v[t] + v[F + t] : v[t];
+      s_tot = tot;
+    }
+    __syncthreads();
+    const double tot = s_tot;  // (written again behind the next sweep's barriers only)
+    if (!(tot > 0.0)) {        // no consistent path: the host writes the input genotype
+      if (tid == 0) s.status[q] = 3;
+      continue;
+    }
+    // the maxima: raw doubles in the regular range, and again with rescaled records if those underflow
+    if constexpr (EXT) {
+      given_sweep<false, true>(a, roff, xo, ev, ne, &flag, top);
+    } else {
+      if (tid == 0) flag = 0;
+      __syncthreads();
+      given_sweep<false, false>(a, roff, xo, ev, ne, &flag, top);
+      if (flag != 0) given_sweep<false, true>(a, roff, xo, ev, ne, &flag, top);  // block-uniform: read behind the sweep's last barrier
+    }
+    auto kind = [&](int j) { return ((const int32_t *)(a.x + xo[j] + 4ull * a.rec[roff[j]]))[1]; };
+    // the final record's best candidate
+    const RecView RL(a.rec + roff[L], L == hl);
+    const double *vL = (const double *)(a.x + xo[L]);
+    double best = -1.0;
+    unsigned bkey = 0xFFFFFFFFu;
+    for (int t = tid; t < RL.F; t += NT) {  // ascending: strictly larger only
+      const double h = vL[t], d = vL[RL.F + t];
+      if (h > best) {
+        best = h;
+        bkey = 2u * (unsigned)t;
+      }
+      if (d > best) {
+        best = d;
+        bkey = 2u * (unsigned)t + 1u;
+      }
+    }
+    wave_best(best, bkey);
+    if (lane == 0) {
+      bv[wave] = best;
+      bk[wave] = bkey;
+    }
+    __syncthreads();
+    if (wave != 0) continue;  // (wave 0 passes the next individual's barriers after its traceback)
+    best = bv[0];
+    bkey = bk[0];
+    for (int w = 1; w < nw; ++w)
+      if (bv[w] > best || (bv[w] == best && bk[w] < bkey)) {
+        best = bv[w];
+        bkey = bk[w];
+      }
+    if (!(best > 0.0)) {  // (the sums found a path, so the maxima do)
+      if (lane == 0) s.status[q] = 1;
+      continue;
+    }
+    auto put = [&](int k, int side, uint32_t x) {
+      if (s.al && lane == 0) s.al[((size_t)q * 2 + side) * L + k] = (uint8_t)x;
+    };
+    int t = (int)(bkey >> 1);
+    unsigned lab = bkey & 1u;  // plain record: h = 0, d = 1; span record: c
+    int par = 0;
+    bool het = false, dead = false;
+    double p = 1.0;
+    int pe = 0;  // the true product is p 2^pe
+    auto renorm = [&]() {
+      int e;
+      p = frexp(p, &e);
+      pe += e;
+    };
+    for (int j = L; j > hl; --j) {  // wave-uniform
+      const RecView R(a.rec + roff[j], false);
+      const uint32_t hd = R.hdr[t], xa = hd & 0xFFu, xb = (hd >> 8) & 0xFFu;
+      const uint32_t r0 = R.cb[t], r1 = R.cb[t + 1];
+      const double tpv = R.tpv[t];
+      const int Fq = (int)a.rec[roff[j - 1]];
+      const double *p0 = (const double *)(a.x + xo[j - 1]), *p1 = p0 + Fq;
+      const int kj = kind(j);
+      const bool cont = kj & 2, labels = kj & 1, below = kind(j - 1) & 1;
+      put(j - 1, par, xa);
+      put(j - 1, par ^ 1, xb);
+      het |= xa != xb;
+      p = j == L ? tpv : p * tpv;
+      renorm();
+      // 0 inside; 1 over a span record; 2 Vd' then 2 Vh'; 3 the label's own value
+      const int mode = cont ? 0 : below ? 1 : (labels || (lab == 1u && xa != xb)) ? 2 : 3;
+      double cv = -1.0;
+      unsigned ck = 0xFFFFFFFFu, cw = 0u;
+      for (uint32_t rb = r0; rb < r1; rb += WAVE) {  // 64 contributions at a time; an earlier batch wins a tie
+        const uint32_t r = rb + (uint32_t)lane;
+        double v = -1.0;
+        unsigned k = 0xFFFFFFFFu;
+        uint32_t w = 0u;
+        if (r < r1) {
+          w = R.ct[r];
+          const uint32_t ps = cw_state(w);
+          k = 2u * (unsigned)lane;
+          if (mode == 0) {
+            v = (lab ^ (cw_rev(w) ? 1u : 0u)) ? p1[ps] : p0[ps];
+          } else if (mode == 1) {
+            if (!labels && lab == 0u) {
+              v = 0.0;  // (Vh is 0 above a span: never chosen)
+            } else {
+              const double d0 = p0[ps], d1 = p1[ps];
+              v = d0;
+              if (d1 > d0) {
+                v = d1;
+                k += 1u;
+              }
+            }
+          } else if (mode == 2) {
+            const double d = p1[ps], h2 = 2.0 * p0[ps];
+            v = d;
+            if (h2 > d) {
+              v = h2;
+              k += 1u;
+            }
+          } else {
+            v = lab ? p1[ps] : p0[ps];
+          }
+        }
+        wave_best(v, k);
+        if (v > cv) {
+          cv = v;
+          ck = k;
+          cw = __shfl(w, (int)(k >> 1));
+        }
+      }
+      if (!(cv > 0.0)) {  // (a state no path reaches is never chosen; if one were, the individual counts as unresolved)
+        dead = true;
+        break;
+      }
+      if (mode == 0) lab ^= cw_rev(cw) ? 1u : 0u;
+      else if (mode == 1) lab = ck & 1u;
+      else if (mode == 2) lab = (ck & 1u) ? 0u : 1u;
+      if (cw_rev(cw)) par ^= 1;
+      t = (int)cw_state(cw);
+    }
+    if (!dead) {  // the head state: loci below head_len
+      const RecView H(a.rec + roff[hl], true);
+      const double tpv = H.tpv[t];
+      p = L == hl ? tpv : p * tpv;
+      renorm();
+      if (hl == 1) {
+        const uint32_t hd = H.hdr[t], xa = hd & 0xFFu, xb = (hd >> 8) & 0xFFu;
+        put(0, par, xa);
+        put(0, par ^ 1, xb);
+        het |= xa != xb;
+      } else {
+        const uint32_t *plo = H.cb + H.F + 1, *phi = plo + H.F;
+        const uint8_t *pa = a.head_al + (size_t)plo[t] * hl, *pb = a.head_al + (size_t)phi[t] * hl;
+        for (int k = 0; k < hl; ++k) {
+          put(k, par, pa[k]);
+          put(k, par ^ 1, pb[k]);
+          het |= pa[k] != pb[k];
+        }
+      }
+    }
+    if (lane == 0) {
+      if (dead) s.status[q] = 1;
+      if (s.prob) s.prob[q] = dead ? 0.0 : ldexp((het ? p * 2.0 : p) / pg, pe - pge);
+      if (s.evidence) {
+        int ge;
+        const double gm = frexp(pg, &ge);
+        s.evidence[q] = dead ? 0.0 : ldexp(tot / gm, -es - pge - ge);
+      }
+    }
+  }
+}
+
+hipError_t launch_exact_map_phase_given(const ExactArgs &a, const GivenArgs &s, int grid, hipStream_t st, int block) {
+  if (a.n_order <= 0) return hipSuccess;
+  if (grid < 1 || !s.status || !s.ev_off || !s.ev || block < WAVE || block > 256 || block % WAVE) return hipErrorInvalidValue;
+  if (a.extended) hipLaunchKernelGGL(exact_map_phase_given<true>, dim3(grid), dim3(block), 0, st, a, s);
+  else hipLaunchKernelGGL(exact_map_phase_given<false>, dim3(grid), dim3(block), 0, st, a, s);
+  return hipGetLastError();
+}
+
 // Ranked phasings (hmc_ranked_phasings): the k haplotype pairs of largest
 // exact posterior, each once, with its posterior — exact_map_phase from
 // max-product to list max-product.  State t of a record keeps two descending

@@ -1,6 +1,7 @@
 // exact.hpp — device arguments of the exact M-step kernels (exact.hip).
 #pragma once
 #include "dosage_plan.hpp"
+#include "evidence_plan.hpp"
 #include "hmc_internal.hpp"
 
 namespace hmc {
@@ -241,6 +242,25 @@ struct MapArgs {
 };
 // after exact_fb (forward only will do) over the same group; block sizes 64 .. 256 and the grid do not change the bits
 hipError_t launch_exact_map_phase(const ExactArgs &a, const MapArgs &s, int grid, hipStream_t st, int block = 256);
+
+// MAP phasing given phase sets (exact_map_phase_given): exact_map_phase over
+// the pairs consistent with caller-given evidence, and P(evidence | genotype).
+// Per individual of the shard (batch index) the host plan's events
+// (evidence_plan.hpp: constrained loci ascending, a set's first and last
+// marked) as a CSR; the kernel never searches the caller's entries.  Two
+// sweeps over the x-store slots exact_fb's forward-only pass has laid out —
+// sums, then maxima — and exact_map_phase's traceback; outputs as MapArgs,
+// plus evidence[slot].  Status 3: no consistent path (the sums come to 0).
+struct GivenArgs {
+  const unsigned long long *ev_off = nullptr;  // [batch + 1]
+  const GivenEvent *ev = nullptr;
+  uint8_t *al = nullptr;           // [slots][2][L] allele indices
+  double *prob = nullptr;          // [slots]
+  double *evidence = nullptr;      // [slots]
+  int32_t *status = nullptr;       // [slots] 0 ok, 1 unresolved, 2 P(genotype) subnormal, 3 no consistent path
+};
+// after exact_fb (forward only will do) over the same group; block sizes 64 .. 256 and the grid do not change the bits
+hipError_t launch_exact_map_phase_given(const ExactArgs &a, const GivenArgs &s, int grid, hipStream_t st, int block = 256);
 
 // Ranked phasings (exact_ranked_phasings): the k haplotype pairs of largest
 // exact posterior of every individual of the group, each once, by a list

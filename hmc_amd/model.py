@@ -733,6 +733,54 @@ class HaploModel:
         """map_phase of the whole shard as text, three lines per individual (hmc_write_map_phase)."""
         self._check(lib().hmc_write_map_phase(self._h, path.encode()))
 
+    @staticmethod
+    def _evidence_arrays(evidence):
+        """evidence: rows (individual, locus, set, first allele symbol), as an
+        [n_ev, 4] integer array or a sequence of such rows -> four int32 columns."""
+        ev = np.asarray(evidence if len(evidence) else np.zeros((0, 4)), np.int64).reshape(-1, 4)
+        return [np.ascontiguousarray(ev[:, c], np.int32) for c in range(4)]
+
+    def map_phase_given(self, evidence, indiv=None) -> dict:
+        """map_phase over the haplotype pairs consistent with phase evidence
+        (hmc_map_phase_given).  evidence: rows (individual, locus, set, allele)
+        — in phase set `set` (a name only) of panel individual `individual` the
+        allele with symbol `allele` at `locus` lies on the set's first
+        haplotype; rows of individuals not asked for are ignored.  Returns
+        hap[n, 2, L], prob[n] (the pair's posterior given the genotype alone,
+        the number map_phase and ranked_phasings give that pair), evidence[n]
+        = P(evidence | genotype), given[n] = prob / evidence (0 where the
+        status is not 0), status[n] (0 ok; 1, 2 as map_phase; 3 no pair is
+        consistent with the evidence: the input genotype, zeros)."""
+        if indiv is None:
+            qi, n = None, self.i1 - self.i0
+        else:
+            qi = np.ascontiguousarray(indiv, np.int32).reshape(-1)
+            n = len(qi)
+        ei, el, es, ef = self._evidence_arrays(evidence)
+        out = dict(hap=np.zeros((n, 2, self.L), np.int32), prob=np.zeros(n, np.float64), evidence=np.zeros(n, np.float64),
+                   status=np.zeros(n, np.int32))
+        self._check(lib().hmc_map_phase_given(self._h, n, None if qi is None else _p(qi, C.c_int32), len(ei), _p(ei, C.c_int32),
+                                              _p(el, C.c_int32), _p(es, C.c_int32), _p(ef, C.c_int32), _p(out["hap"], C.c_int32),
+                                              _p(out["prob"], C.c_double), _p(out["evidence"], C.c_double),
+                                              _p(out["status"], C.c_int32)))
+        ok = out["status"] == 0
+        out["given"] = np.where(ok, out["prob"] / np.where(ok, out["evidence"], 1.0), 0.0)
+        return out
+
+    def given_stats(self) -> dict:
+        """Device ms and counts of the last map_phase_given (hmc_last_given_stats)."""
+        s, f, k = C.c_double(), C.c_double(), C.c_double()
+        g, p, c = C.c_int(), C.c_int(), C.c_int()
+        self._check(lib().hmc_last_given_stats(self._h, C.byref(s), C.byref(f), C.byref(k), C.byref(g), C.byref(p), C.byref(c)))
+        return dict(structure_ms=s.value, fb_ms=f.value, sweep_ms=k.value, groups=g.value, n_pruned=p.value,
+                    n_constrained=c.value)
+
+    def write_map_phase_given(self, path: str, evidence):
+        """map_phase_given of the whole shard as text, three lines per individual (hmc_write_map_phase_given)."""
+        ei, el, es, ef = self._evidence_arrays(evidence)
+        self._check(lib().hmc_write_map_phase_given(self._h, path.encode(), len(ei), _p(ei, C.c_int32), _p(el, C.c_int32),
+                                                    _p(es, C.c_int32), _p(ef, C.c_int32)))
+
     def ranked_phasings(self, k: int, indiv=None) -> dict:
         """The k most probable haplotype pairs under the model of the last
         resolve_all, each once, with their exact posteriors

@@ -564,6 +564,90 @@ int hmc_map_phase(hmc_ctx *ctx, int64_t n, const int32_t *indiv, int32_t *hap, d
  * groups the individuals ran in; individuals on pruned records.  Replaces no
  * reference interface. */
 int hmc_last_map_stats(const hmc_ctx *ctx, double *structure_ms, double *fb_ms, double *sweep_ms, int *groups, int *n_pruned);
+/* MAP phasing given phase sets: hmc_map_phase over the haplotype pairs that
+ * are consistent with caller-given phase evidence (what a read pair, a trio or
+ * an assembly fixes, as VCF's 0|1 with a PS tag writes it), and the
+ * probability of that evidence.  A variable-order chain couples the switches,
+ * so the answer is not hmc_map_phase's with a few loci flipped.
+ * indiv[n], hap[n][2][L], prob[n], status[n] as for hmc_map_phase (indiv = NULL:
+ * the whole shard); evidence[n]; any output may be NULL.
+ *   Entries.  Entry e of n_ev says: for individual ev_indiv[e] (a panel
+ *   index), in phase set ev_set[e] (any int32, a name only), the allele with
+ *   symbol ev_first[e] at locus ev_locus[e] lies on that set's first haplotype;
+ *   the individual's other input allele there lies on the set's second.
+ *   Entries come in any order; entries of individuals not asked for in this
+ *   call (or outside this rank's shard) are ignored, so one table serves many
+ *   calls; a set of a single locus constrains nothing and is allowed.
+ *   Meaning.  A pair {h0, h1} is consistent with a set when one of its two
+ *   haplotypes carries the first-haplotype allele at every locus of the set —
+ *   which of the two may differ from set to set — and with the evidence when it
+ *   is consistent with every set of the individual.
+ *   hap is the consistent pair of largest exact posterior P(pair | genotype),
+ *   prob that posterior by hmc_map_phase's rule (same order, same mantissa and
+ *   exponent bookkeeping: a pair keeps the one number it has in hmc_map_phase,
+ *   hmc_ranked_phasings and the draws), evidence = P(evidence | genotype), the
+ *   sum of the posteriors of all consistent pairs.  The posterior given the
+ *   evidence is prob / evidence; the caller divides.
+ *   Status 0 / 1 / 2 exactly where hmc_map_phase puts them; 3: the lattice has a
+ *   path but none consistent with the evidence (the computed evidence is
+ *   exactly 0; this includes an individual swept over pruned records).  Rows
+ *   of status 1, 2 and 3 carry the input genotype, prob 0 and evidence 0.
+ *   An individual with no entries, or with single-locus sets only, gets
+ *   hmc_map_phase's bytes and evidence exactly 1.0.
+ *
+ * The sweep.  A set needs an orientation label c per state: its first
+ * haplotype lies on the state's a side (c = 0) or b side (c = 1); a
+ * predecessor's label c arrives as c ^ rev(r).  Every path through a set's
+ * first locus is heterozygous from there on, so between a set's first and last
+ * locus the two values of a state are (V[0], V[1]) by label (a span record),
+ * and elsewhere hmc_map_phase's (Vh, Vd).  The record of locus k is k + 1 (the
+ * head record for k < head_len).  State t with alleles (xa, xb):
+ *   first locus of a set:  m = max_r max(Vd'[pred r], 2.0 * Vh'[pred r]), or
+ *     max_r max(V'[0][pred r], V'[1][pred r]) when the record below ends the
+ *     previous set; V[0][t] = tpv[t] * m if xa is the first-haplotype allele,
+ *     V[1][t] = tpv[t] * m if xb is, the other label 0;
+ *   further up to the set's last locus:  V[c][t] = tpv[t] * max_r V'[c ^ rev(r)][pred r];
+ *     at a locus of the set the label whose side does not carry the
+ *     first-haplotype allele is stored as 0, at other loci both labels pass;
+ *   the record above a set's last:  hmc_map_phase's recurrence with
+ *     Vd' = max(V'[0], V'[1]) and Vh' = 0.
+ *   Loci below head_len are matched at the head record from the states' head
+ *   patterns; for an individual with a missing allele at a head locus those
+ *   loci come from the reference's head pairing, so for evidence that touches
+ *   them only consistency holds.
+ *   Tie rules.  Final record: candidates (t, label) in order of t, label 0
+ *   (Vh or V[0]) before label 1; the largest value, among equals the first.
+ *   Going down, the first contribution in record order that attains the
+ *   maximum; where a contribution offers two values — Vd' then 2.0 * Vh', or
+ *   V'[0] then V'[1] — the first of equals.  A label stored as 0 is never
+ *   chosen.  Spelling and prob as hmc_map_phase.
+ *   evidence is the same sweep with ordered sums in place of maxima
+ *   (contributions in record order; the final record in state order), every
+ *   record rescaled by a power of two in both ranges, divided by the range's
+ *   P(genotype).  Mirror paths need no care: both pass or both fail every set.
+ * The bits of a row depend on the model, the range, the individual and its own
+ * set of entries: not on entry order, the integers used as set names, other
+ * individuals or their evidence, batches, launch shapes, store budgets or
+ * sharding; flipping a set wholesale (ev_first replaced by the other input
+ * allele at every locus of the set) changes no byte.
+ * HMC_EARG, with a message naming the first offending entry: ev_indiv outside
+ * the panel; a locus out of range; a locus where the individual's input is not
+ * heterozygous with both alleles present; ev_first neither of the two input
+ * alleles; the same (individual, locus) in two entries.  HMC_EUNSUPPORTED,
+ * naming the individual: two of its sets interleave ([first locus, last locus]
+ * overlap).  Otherwise HMC_EARG and HMC_EUNSUPPORTED as for hmc_map_phase.
+ * Needs a preceding hmc_resolve_all; runs its own exact-mode structure pass and
+ * forward pass over the individuals asked for only and changes no later
+ * result.  n = 0 is HMC_OK with no device work and zeroed stats.  Replaces no
+ * reference interface. */
+int hmc_map_phase_given(hmc_ctx *ctx, int64_t n, const int32_t *indiv, int64_t n_ev, const int32_t *ev_indiv,
+                        const int32_t *ev_locus, const int32_t *ev_set, const int32_t *ev_first, int32_t *hap, double *prob,
+                        double *evidence, int32_t *status);
+/* Last hmc_map_phase_given: as hmc_last_map_stats, and the individuals that
+ * ran the constrained sweep (the others took hmc_map_phase's).  Replaces no
+ * reference interface. */
+int hmc_last_given_stats(const hmc_ctx *ctx, double *structure_ms, double *fb_ms, double *sweep_ms, int *groups, int *n_pruned,
+                         int *n_constrained);
 /* Ranked phasings: the k haplotype pairs of largest exact posterior P(pair |
  * genotype) under the model of the last E-step, each once, with its posterior
  * — what "MAP pair, posterior 0.41" leaves open: the top diplotypes with their
@@ -827,6 +911,22 @@ int hmc_write_posterior_draws(hmc_ctx *ctx, const char *path, int draws, uint64_
  * for a missing input allele in a row of status 1 or 2).  Needs a preceding
  * hmc_resolve_all or hmc_run.  Replaces no reference interface. */
 int hmc_write_map_phase(hmc_ctx *ctx, const char *path);
+/* hmc_map_phase_given of the whole shard as text (hmc_resolve
+ * --output-map-given FILE --evidence EVFILE): hmc_write_map_phase's three-line
+ * form with the header "Id\tStatus\tPosterior\tEvidence", both numbers as
+ * %.17g.  Replaces no reference interface. */
+int hmc_write_map_phase_given(hmc_ctx *ctx, const char *path, int64_t n_ev, const int32_t *ev_indiv, const int32_t *ev_locus,
+                              const int32_t *ev_set, const int32_t *ev_first);
+/* The evidence file of hmc_resolve --evidence into the four entry arrays:
+ * tab-separated lines "Id  Marker  Set  Allele" with ids and marker names as
+ * the loaded genotype files give them, Set an integer, the allele spelled as
+ * the genotype files spell alleles; empty lines are skipped, and so are lines
+ * starting with '#' unless they have four fields of which the first is an
+ * individual's id (PHASE files give ids that start with '#').  *n_ev gets the number of entries; at most cap are written (call
+ * with cap = 0 first).  HMC_EARG with a message naming the line.  Replaces no
+ * reference interface. */
+int hmc_read_evidence(hmc_ctx *ctx, const char *path, int64_t *n_ev, int32_t *ev_indiv, int32_t *ev_locus, int32_t *ev_set,
+                      int32_t *ev_first, int64_t cap);
 /* hmc_ranked_phasings of the whole shard as text (hmc_resolve --output-ranked
  * FILE --ranked K): the header "Id\tRank\tPosterior\tHaplotype0\tHaplotype1",
  * then one line per individual of status 0 and per rank < count,

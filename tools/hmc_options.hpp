@@ -25,6 +25,8 @@ struct Options {
   std::string output_dosages;          // --output-dosages FILE
   std::string haplotypes;              // --haplotypes HAPFILE (required with it)
   std::string output_map;              // --output-map FILE
+  std::string output_map_given;        // --output-map-given FILE
+  std::string evidence;                // --evidence EVFILE (required with it)
   std::string output_ranked;           // --output-ranked FILE
   int ranked = 4;                      // --ranked K (1 .. 16)
   bool have_ranked = false;
@@ -65,10 +67,14 @@ constexpr const char *USAGE =
     "                        start the 0-based first locus, alleles as the genotype files spell them, ? = any)\n"
     "  --output-map FILE     write FILE: for every individual the most probable haplotype pair under the\n"
     "                        final model, found exactly (no k-best cut), with its status and posterior\n"
+    "  --output-map-given FILE --evidence EVFILE  write FILE: as --output-map, over the haplotype pairs\n"
+    "                        consistent with the phase sets of EVFILE (tab-separated lines: Id Marker Set\n"
+    "                        Allele — the allele on the set's first haplotype, as the genotype files spell\n"
+    "                        it; # starts a comment line), with the probability of that evidence\n"
     "  --output-ranked FILE [--ranked K]  write FILE: for every individual the K most probable haplotype\n"
     "                        pairs under the final model, each once, in order, with their posteriors\n"
     "                        (default K = 4, at most 16; an exact ranking, no k-best cut)\n"
-    "  --extended-range      the seven options above in extended range: individuals whose likelihood\n"
+    "  --extended-range      the eight options above in extended range: individuals whose likelihood\n"
     "                        underflows a double (panels of more than about 1 200 loci) get lines too";
 
 // 0 on success; otherwise `err` says what is wrong (a missing value, an
@@ -104,6 +110,8 @@ inline int parse_options(int argc, const char *const *argv, Options &o, std::str
     else if (a == "--draws") { if (!next()) return 1; o.draws = atoi(v); o.have_draws = true; }
     else if (a == "--output-dosages") { if (!next()) return 1; o.output_dosages = v; }
     else if (a == "--output-map") { if (!next()) return 1; o.output_map = v; }
+    else if (a == "--output-map-given") { if (!next()) return 1; o.output_map_given = v; }
+    else if (a == "--evidence") { if (!next()) return 1; o.evidence = v; }
     else if (a == "--output-ranked") { if (!next()) return 1; o.output_ranked = v; }
     else if (a == "--ranked") { if (!next()) return 1; o.ranked = atoi(v); o.have_ranked = true; }
     else if (a == "--haplotypes") { if (!next()) return 1; o.haplotypes = v; }
@@ -139,6 +147,10 @@ inline int parse_options(int argc, const char *const *argv, Options &o, std::str
     err = "--output-dosages FILE and --haplotypes HAPFILE need each other\n" + std::string(USAGE);
     return 1;
   }
+  if (o.output_map_given.empty() != o.evidence.empty()) {
+    err = "--output-map-given FILE and --evidence EVFILE need each other\n" + std::string(USAGE);
+    return 1;
+  }
   if (!o.output_ranked.empty() && (o.ranked < 1 || o.ranked > 16)) {
     err = "--output-ranked needs --ranked K with 1 <= K <= 16\n" + std::string(USAGE);
     return 1;
@@ -148,8 +160,9 @@ inline int parse_options(int argc, const char *const *argv, Options &o, std::str
     return 1;
   }
   if (o.extended_range && !o.output_posteriors && !o.output_switch_posteriors && o.output_pair_posteriors.empty() &&
-      o.output_draws.empty() && o.output_dosages.empty() && o.output_map.empty() && o.output_ranked.empty()) {
-    err = "--extended-range needs --output-posteriors, --output-switch-posteriors, --output-pair-posteriors, --output-draws, --output-dosages, --output-map or --output-ranked\n" +
+      o.output_draws.empty() && o.output_dosages.empty() && o.output_map.empty() && o.output_map_given.empty() &&
+      o.output_ranked.empty()) {
+    err = "--extended-range needs --output-posteriors, --output-switch-posteriors, --output-pair-posteriors, --output-draws, --output-dosages, --output-map, --output-map-given or --output-ranked\n" +
           std::string(USAGE);
     return 1;
   }

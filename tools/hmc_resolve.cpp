@@ -14,6 +14,7 @@
 //               [--output-pair-posteriors FILE --pair-span K]
 //               [--output-draws FILE [--draws 100] [--seed 0]]
 //               [--output-dosages FILE --haplotypes HAPFILE] [--output-map FILE]
+//               [--output-map-given FILE --evidence EVFILE]
 //               [--output-ranked FILE [--ranked 4]] [--extended-range] [--device 0] datafile ...
 // --output-posteriors (no reference counterpart) writes <first file>.posteriors:
 // genotype posteriors at the loci with a missing input allele, under the final
@@ -32,10 +33,14 @@
 // --output-map FILE (none either) writes FILE: every individual's most
 // probable haplotype pair under the final model, found exactly, with its
 // status and posterior (hmc_write_map_phase).
+// --output-map-given FILE --evidence EVFILE (none either) writes FILE: as
+// --output-map over the haplotype pairs consistent with the phase sets listed
+// in EVFILE (hmc_read_evidence), with the probability of that evidence
+// (hmc_write_map_phase_given).
 // --output-ranked FILE [--ranked K] (none either) writes FILE: every
 // individual's K most probable haplotype pairs under the final model, each
 // once, in order, with their posteriors (hmc_write_ranked_phasings).
-// --extended-range (none either) runs those seven in extended range
+// --extended-range (none either) runs those eight in extended range
 // (hmc_set_posterior_range): individuals whose likelihood underflows a double
 // get lines too.
 #include <cstdio>
@@ -99,6 +104,18 @@ int main(int argc, char **argv) {
       return 1;
     }
   }
+  std::vector<int32_t> ev_i, ev_l, ev_s, ev_f;
+  if (!o.evidence.empty()) {  // read before the run: a malformed file fails at once
+    int64_t n_ev = 0;
+    if ((rc = hmc_read_evidence(ctx, o.evidence.c_str(), &n_ev, nullptr, nullptr, nullptr, nullptr, 0))) die("hmc_read_evidence");
+    ev_i.resize((size_t)n_ev + 1);
+    ev_l.resize((size_t)n_ev + 1);
+    ev_s.resize((size_t)n_ev + 1);
+    ev_f.resize((size_t)n_ev + 1);
+    if ((rc = hmc_read_evidence(ctx, o.evidence.c_str(), &n_ev, ev_i.data(), ev_l.data(), ev_s.data(), ev_f.data(), n_ev)))
+      die("hmc_read_evidence");
+    ev_i.resize((size_t)n_ev);
+  }
   hmc_iter_log log[256];
   int iters = 0, np0 = 0;
   double t_m0 = 0;
@@ -149,6 +166,11 @@ int main(int argc, char **argv) {
   }
   if (!o.output_map.empty()) {  // of the same E-step
     if ((rc = hmc_write_map_phase(ctx, o.output_map.c_str()))) die("hmc_write_map_phase");
+  }
+  if (!o.output_map_given.empty()) {  // of the same E-step
+    if ((rc = hmc_write_map_phase_given(ctx, o.output_map_given.c_str(), (int64_t)ev_i.size(), ev_i.data(), ev_l.data(),
+                                        ev_s.data(), ev_f.data())))
+      die("hmc_write_map_phase_given");
   }
   if (!o.output_ranked.empty()) {  // of the same E-step
     if ((rc = hmc_write_ranked_phasings(ctx, o.output_ranked.c_str(), o.ranked))) die("hmc_write_ranked_phasings");
