@@ -1,4 +1,4 @@
-// dosage_plan.hpp — the host plan of hmc_haplotype_dosages (exact.hip,
+// dosage_plan.hpp — the host plan of hmc_haplotype_dosages (exact_query.hip,
 // exact_haplotype_dosages).  Free of HIP and of the context so that the host
 // sanitizer program (tests/sanitize/dosage_main.cpp) can drive it.
 #pragma once

@@ -1,4 +1,4 @@
-// evidence_plan.hpp — the host plan of hmc_map_phase_given (exact.hip,
+// evidence_plan.hpp — the host plan of hmc_map_phase_given (exact_query.hip,
 // exact_map_phase_given) and the evidence file reader of hmc_resolve
 // --evidence.  Free of HIP and of the context so that the host sanitizer
 // program (tests/sanitize/evidence_main.cpp) can drive it.

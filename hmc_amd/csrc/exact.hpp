@@ -1,4 +1,5 @@
-// exact.hpp — device arguments of the exact M-step kernels (exact.hip).
+// exact.hpp — device arguments of the exact M-step kernels (exact.hip) and of
+// the posterior queries over the same records (exact_query.hip).
 #pragma once
 #include "dosage_plan.hpp"
 #include "evidence_plan.hpp"

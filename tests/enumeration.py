@@ -500,8 +500,8 @@ def check_mstep(new: dict, alleles: np.ndarray, prev: dict, head_len: int, fixed
 
     Fixed-point part (`fixed_point`: the library and the device-order
     restatement): each individual's term is rounded to a multiple of 2^-44
-    before it is added (exact.hpp:9 EXACT_FIXED_SCALE, exact.hip:610-611 and
-    :897-898 __double2ll_rn(freq * 2^44), one addend per individual and
+    before it is added (exact.hpp:9 EXACT_FIXED_SCALE, exact.hip:604-605 and
+    :891-892 __double2ll_rn(freq * 2^44), one addend per individual and
     pattern; hmc_oracle.cpp xwalk llrint), the integer total converts exactly
     (N 2^44 < 2^53) and is divided by N (ctx_exact.cpp:160-164): at most
     N * 2^-45 on f and pre, 2^-45 absolute on freq and prefix.

@@ -158,8 +158,8 @@ def test_mined_tables(name):
 def test_exact_mstep(name):
     """One exact M-step (exact_estimate) after M0 and E1.  Bound
     (enumeration.check_mstep): per frequency N addends, each rounded to a
-    multiple of the fixed-point quantum 2^-44 (exact.hpp:9, exact.hip:610-611
-    and :897-898, ctx_exact.cpp:160-164), so N * 2^-45 / N = 2^-45 absolute on
+    multiple of the fixed-point quantum 2^-44 (exact.hpp:9, exact.hip:604-605
+    and :891-892, ctx_exact.cpp:160-164), so N * 2^-45 / N = 2^-45 absolute on
     freq and prefix, plus gamma(max_i (6L + 8 + 3 M_i) + N + 1) relative for
     the floating-point walk; on these panels that is below 1e-9 relative at
     the smallest non-zero frequency (asserted)."""

@@ -1,4 +1,4 @@
-"""hmc_haplotype_dosages (exact.hip exact_haplotype_dosages) on the GPU: the
+"""hmc_haplotype_dosages (exact_query.hip exact_haplotype_dosages) on the GPU: the
 exact expected copies of caller-given haplotypes — against exhaustive
 enumeration (tests/dosage_enumeration.py), against itself across every
 schedule (slots per state NS, rounds, the LDS tier, pattern order, duplicates,

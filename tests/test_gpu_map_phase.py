@@ -1,4 +1,4 @@
-"""hmc_map_phase (exact.hip exact_map_phase) on the GPU: the most probable
+"""hmc_map_phase (exact_query.hip exact_map_phase) on the GPU: the most probable
 haplotype pair and its exact posterior, against exhaustive enumeration
 (tests/map_enumeration.py), against the E-step's k-best beam and the posterior
 draws, and against itself across everything the result must not depend on.

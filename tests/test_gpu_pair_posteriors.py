@@ -1,4 +1,4 @@
-"""hmc_pair_posteriors (exact.hip exact_pair_posteriors) on the GPU: for
+"""hmc_pair_posteriors (exact_query.hip exact_pair_posteriors) on the GPU: for
 caller-given pairs (a, b) of heterozygous loci of an individual, any distance
 apart, the posterior that their lower alleles share a haplotype (cis) and that
 they do not (trans) — against exhaustive enumeration

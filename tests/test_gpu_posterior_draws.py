@@ -1,4 +1,4 @@
-"""hmc_posterior_draws (exact.hip exact_posterior_draws) on the GPU: whole
+"""hmc_posterior_draws (exact_query.hip exact_posterior_draws) on the GPU: whole
 haplotype pairs drawn from the exact posterior, against exhaustive enumeration
 (tests/draw_enumeration.py), against the marginals the library already pins
 (switch and genotype posteriors) and against itself across everything a draw

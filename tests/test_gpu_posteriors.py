@@ -1,4 +1,4 @@
-"""hmc_genotype_posteriors (exact.hip exact_site_posteriors) on the GPU: the
+"""hmc_genotype_posteriors (exact_query.hip exact_site_posteriors) on the GPU: the
 posterior of the unordered genotype at every locus with a missing input
 allele, against exhaustive enumeration (tests/posterior_enumeration.py) and
 against itself across groupings and shards.

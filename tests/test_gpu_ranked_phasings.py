@@ -1,4 +1,4 @@
-"""hmc_ranked_phasings (exact.hip exact_ranked_phasings) on the GPU: the k most
+"""hmc_ranked_phasings (exact_query.hip exact_ranked_phasings) on the GPU: the k most
 probable haplotype pairs, each once, with their exact posteriors — against
 exhaustive enumeration (tests/ranked_enumeration.py), against hmc_map_phase
 (row 0, byte for byte), against itself across k and everything else the result

@@ -1,4 +1,4 @@
-"""hmc_switch_posteriors (exact.hip exact_switch_posteriors) on the GPU: for
+"""hmc_switch_posteriors (exact_query.hip exact_switch_posteriors) on the GPU: for
 every pair of consecutive heterozygous loci of an individual the posterior
 that their lower alleles share a haplotype (cis) and that they do not (trans),
 against exhaustive enumeration (tests/switch_enumeration.py) and against
