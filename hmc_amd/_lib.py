@@ -96,6 +96,11 @@ _SIGS = [
     ("hmc_set_dosage_tuning", _i, [_vp, _i, _i]),
     ("hmc_write_haplotype_dosages", _i, [_vp, _cp, _i, _P(_cp), _P(C.c_int32), _P(C.c_int32), _i, _P(C.c_int32),
                                          _P(C.c_int32)]),
+    ("hmc_window_phasings", _i, [_vp, C.c_int64, _P(C.c_int32), _i, _P(C.c_int32), _P(C.c_int32), _i, _i, _P(C.c_int32),
+                                 _P(_d), _P(C.c_int32), _P(C.c_int32), _P(C.c_int32)]),
+    ("hmc_last_window_stats", _i, [_vp, _P(_d), _P(_d), _P(_d), _P(_i), _P(_i), _P(_i), _P(_i), _P(_i)]),
+    ("hmc_set_window_tuning", _i, [_vp, _i, _i]),
+    ("hmc_write_window_phasings", _i, [_vp, _cp, _i, _P(C.c_int32), _P(C.c_int32), _i]),
     ("hmc_posterior_draws", _i, [_vp, C.c_int64, _P(C.c_int32), _i, _u64, _P(C.c_int32), _P(_d), _P(C.c_int32)]),
     ("hmc_last_draw_stats", _i, [_vp, _P(_d), _P(_d), _P(_d), _P(_i), _P(_i)]),
     ("hmc_map_phase", _i, [_vp, C.c_int64, _P(C.c_int32), _P(C.c_int32), _P(_d), _P(C.c_int32)]),

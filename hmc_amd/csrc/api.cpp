@@ -1127,6 +1127,34 @@ int hmc_last_ranked_stats(const hmc_ctx *h, double *structure_ms, double *fb_ms,
   return query_stats(h, Ctx::XP_RANK, structure_ms, fb_ms, sweep_ms, groups, n_pruned, nullptr, nullptr, nullptr, k_built);
 }
 
+int hmc_window_phasings(hmc_ctx *h, int64_t n, const int32_t *indiv, int n_windows, const int32_t *start, const int32_t *len,
+                        int maxlen, int k, int32_t *hap, double *prob, int32_t *count, int32_t *n_config, int32_t *status) {
+  if (!h) return HMC_EARG;
+  Ctx &c = h->c;
+  if (!c.have_panel) return c.fail(HMC_EARG, "no panel loaded");
+  return c.window_phasings(n, indiv, n_windows, start, len, maxlen, k, hap, prob, count, n_config, status);
+}
+
+int hmc_last_window_stats(const hmc_ctx *h, double *structure_ms, double *fb_ms, double *sweep_ms, int *groups, int *n_pruned,
+                          int *n_spilled, int *configs_built, int *n_over_cap) {
+  if (int rc = query_stats(h, Ctx::XP_WINDOW, structure_ms, fb_ms, sweep_ms, groups, n_pruned, n_spilled, nullptr, nullptr,
+                           configs_built))
+    return rc;
+  if (n_over_cap) *n_over_cap = h->c.qstats[Ctx::XP_WINDOW].constrained;
+  return HMC_OK;
+}
+
+int hmc_set_window_tuning(hmc_ctx *h, int max_configs, int tier_states) {
+  if (!h) return HMC_EARG;
+  if (max_configs < 0 || max_configs > hmc::WIN_CAP_MAX)
+    return h->c.fail(HMC_EARG, "window tuning: a cap of %d configurations is outside [0, %d]", max_configs, hmc::WIN_CAP_MAX);
+  if (tier_states < 0 || tier_states > hmc::win_tier_max(4))
+    return h->c.fail(HMC_EARG, "window tuning: a tier of %d states is outside [0, %d]", tier_states, hmc::win_tier_max(4));
+  h->c.wn_cap = max_configs;
+  h->c.wn_tier = tier_states;
+  return HMC_OK;
+}
+
 // Test seam of hmc_ranked_phasings (not in the public header; results do not
 // depend on it): store_bytes = the budget of the list store, which decides how
 // many individuals of a group go through one launch (0: the value store's
@@ -1502,6 +1530,43 @@ int hmc_write_ranked_phasings(hmc_ctx *h, const char *path, int k) {
           fprintf(fp, "%s\t%d\t%.17g", id, r, prob[(size_t)i * k + r]);
           for (int side = 0; side < 2; ++side) spell_alleles(fp, c, hap.data() + (((size_t)i * k + r) * 2 + side) * L, '\t');
           fputc('\n', fp);
+        }
+      });
+}
+
+int hmc_write_window_phasings(hmc_ctx *h, const char *path, int n_windows, const int32_t *start, const int32_t *len, int k) {
+  if (!h || !path || !h->c.have_panel) return HMC_EARG;
+  Ctx &c = h->c;
+  if (n_windows < 0 || (n_windows > 0 && (!start || !len))) return c.fail(HMC_EARG, "window phasings: no windows given");
+  if (k < 1 || k > hmc::WIN_K_MAX) return c.fail(HMC_EARG, "window phasings: k = %d is outside [1, %d]", k, hmc::WIN_K_MAX);
+  const int W = n_windows;
+  int maxlen = 1;
+  for (int w = 0; w < W; ++w) maxlen = std::max(maxlen, len[w]);
+  const size_t per = (size_t)W * k * 2 * maxlen;
+  const int nb = batch_size(c, HAP_BATCH, per);
+  std::vector<int32_t> hap((size_t)nb * per), status((size_t)nb * W), count((size_t)nb * W);
+  std::vector<double> prob((size_t)nb * W * k);
+  return write_batches(
+      c, path, nb, "Id\tWindow\tStart\tLength\tRank\tPosterior\tHaplotype0\tHaplotype1\n",
+      [&](int m, const int32_t *indiv) {
+        return c.window_phasings(m, indiv, W, start, len, maxlen, k, hap.data(), prob.data(), count.data(), nullptr, status.data());
+      },
+      [&](FILE *fp, int i, const char *id) {
+        for (int w = 0; w < W; ++w) {
+          const size_t o = (size_t)i * W + w;
+          for (int r = 0; status[o] == 0 && r < count[o]; ++r) {
+            fprintf(fp, "%s\t%d\t%d\t%d\t%d\t%.17g", id, w, start[w], len[w], r, prob[o * k + r]);
+            for (int side = 0; side < 2; ++side) {
+              const int32_t *row = hap.data() + ((o * k + r) * 2 + side) * maxlen;
+              for (int l = 0; l < len[w]; ++l) {
+                fputc(l ? ' ' : '\t', fp);
+                if (row[l] < 0) fputc('?', fp);
+                else if (c.pan.types[start[w] + l] == 'S') fputc((char)row[l], fp);
+                else fprintf(fp, "%d", row[l]);
+              }
+            }
+            fputc('\n', fp);
+          }
         }
       });
 }

@@ -811,20 +811,21 @@ struct Ctx {
   void site_list(SiteList &sl) const;
   int site_group(const ExactArgs &x, int k, int dev_cu);
   // what the exact group runs after exact_fb in place of the trie walk
-  enum XpMode { XP_OFF = 0, XP_GENOTYPE = 1, XP_SWITCH = 2, XP_PAIR = 3, XP_DRAW = 4, XP_LIK = 5, XP_DOSE = 6, XP_MAP = 7, XP_RANK = 8, XP_GIVEN = 9 };
+  enum XpMode { XP_OFF = 0, XP_GENOTYPE = 1, XP_SWITCH = 2, XP_PAIR = 3, XP_DRAW = 4, XP_LIK = 5, XP_DOSE = 6, XP_MAP = 7, XP_RANK = 8, XP_GIVEN = 9, XP_WINDOW = 10 };
   XpMode xp_mode = XP_OFF;
-  // What the nine queries share (ctx_query.cpp).  Of a kind's last call:
+  // What the ten queries share (ctx_query.cpp).  Of a kind's last call:
   // device ms of the structure passes, of exact_fb and of the kind's own
   // kernels (draws_to_symbols included); groups; individuals on pruned
   // records; individuals whose largest record exceeded the tier; the NS used;
   // rounds (pairs: most of any individual, dosages: sweeps the plan takes); the
   // list width KL of the ranked kernel that ran; launches; individuals that
-  // ran exact_map_phase_given.  A kind leaves at zero what it does not use.  The running pass writes its own kind's record.
+  // ran exact_map_phase_given (window phasings: built = the widest NC that ran,
+  // constrained = the (individual, window) pairs over the cap).  A kind leaves at zero what it does not use.  The running pass writes its own kind's record.
   struct QueryStats {
     double ms_struct = 0, ms_fb = 0, ms_sweep = 0;
     int groups = 0, pruned = 0, spilled = 0, slots = 0, rounds = 0, built = 0, batches = 0, constrained = 0;
   };
-  QueryStats qstats[XP_GIVEN + 1];  // by XpMode
+  QueryStats qstats[XP_WINDOW + 1];  // by XpMode
   // HMC_OK, or the error of a query that cannot run: no E-step yet, a model
   // changed since it, more than 44 alleles per locus
   int query_ready(XpMode kind);
@@ -1005,6 +1006,38 @@ struct Ctx {
   DevBuf<int32_t> d_rk_count;
   uint64_t rk_store_bytes = 0;     // hmc_set_ranked_tuning (test seam): the list store's budget, 0 = the value store's
   uint64_t rank_budget_bytes() const { return rk_store_bytes ? rk_store_bytes : trace_budget * 4; }
+  // Window phasings (hmc_window_phasings): per asked individual and window the
+  // distinct haplotype pairs over the window's loci with their exact
+  // posteriors, ranked; exact_window_phasings per group (XP_WINDOW).  The plan
+  // (window_plan.hpp) is built once per call: per (asked individual, window)
+  // the branching loci as digits and the count C of ordered configurations;
+  // C above the cap is status 4 and takes no device work.  A group's asked
+  // individuals run sorted by the width NC their largest C needs, one width
+  // per launch, in batches whose device output stays within WIN_OUT_BYTES and
+  // whose scratch slices (individuals past the tier) within WIN_SCRATCH_BYTES.
+  // Rows are the caller's: an individual asked for twice is swept once.
+  int window_phasings(int64_t n, const int32_t *indiv, int n_windows, const int32_t *start, const int32_t *len, int maxlen, int k,
+                      int32_t *hap, double *prob, int32_t *count, int32_t *n_config, int32_t *status);
+  int window_group(const ExactArgs &x, const int32_t *ids, const std::vector<int32_t> &fm, int k, int dev_cu);
+  static constexpr size_t WIN_OUT_BYTES = (size_t)512 << 20;
+  static constexpr size_t WIN_SCRATCH_BYTES = (size_t)4 << 30;  // the frontiers past the tier, all individuals of a batch
+  struct WindowCall {  // the running call
+    int W = 0, K = 0, maxlen = 0, over_cap = 0;
+    const int32_t *start = nullptr, *len = nullptr;
+    int32_t *hap = nullptr;
+    double *prob = nullptr;
+    std::vector<int32_t> slot;      // [shard] the individual's place among the asked ones, -1 = not asked
+    std::vector<WinItem> item;      // [asked][W]
+    std::vector<WinDigit> dig;
+    std::vector<int32_t> maxc;      // [asked] the largest C within the cap
+    std::vector<int32_t> cnt, ncfg; // [asked][W] rows written, configurations of positive posterior
+  } wn;
+  DevBuf<WinItem> d_wn_item;
+  DevBuf<WinDigit> d_wn_dig;
+  DevBuf<int32_t> d_wn_start, d_wn_len, d_wn_code, d_wn_count, d_wn_ncfg, d_wn_order, d_wn_status;
+  DevBuf<double> d_wn_prob, d_wn_scratch;
+  DevBuf<unsigned long long> d_wn_sbase;  // [batch + 1] the individuals' scratch slices, in doubles
+  int wn_cap = 0, wn_tier = 0;  // hmc_set_window_tuning (0: WIN_CAP_MAX, the width's win_tier_max)
   DevBuf<unsigned long long> d_site_off;
   DevBuf<int32_t> d_site_locus, d_site_status;
   DevBuf<double> d_site_post;

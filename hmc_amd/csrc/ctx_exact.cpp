@@ -266,6 +266,7 @@ int Ctx::exact_group(const int32_t *ids, int k, const std::function<int(std::vec
   if (xp_mode == XP_MAP) return map_group(x, ids, k, dev_cu);
   if (xp_mode == XP_RANK) return ranked_group(x, ids, k, dev_cu);
   if (xp_mode == XP_GIVEN) return given_group(x, ids, k, dev_cu);
+  if (xp_mode == XP_WINDOW) return window_group(x, ids, fm, k, dev_cu);
   if (xp_mode == XP_LIK) {  // the scaled totals of the group's individuals: nothing runs after exact_fb
     std::vector<double> tot(n);
     std::vector<int32_t> ex(n);

@@ -1,5 +1,5 @@
 // ctx_query.cpp — Ctx members: the posterior queries on the exact lattice (genotype, switch and pair posteriors,
-// posterior draws, genotype likelihoods, haplotype dosages, MAP and ranked phasings, MAP phasing given phase sets).  Each runs the shard through
+// posterior draws, genotype likelihoods, haplotype dosages, MAP and ranked phasings, MAP phasing given phase sets, window phasings).  Each runs the shard through
 // estep_split(order, true) like a round of the exact M-step (xp_pass) with a kernel of its own per group in place of
 // the trie walk (exact_group, ctx_exact.cpp).  The kernels differ; the host code around them is written once here.
 #include "ctx.hpp"
@@ -16,7 +16,8 @@ static const char *const QUERY_NOUN[] = {"",
                                          "haplotype dosages",
                                          "MAP phasing",
                                          "ranked phasings",
-                                         "MAP phasing given evidence"};
+                                         "MAP phasing given evidence",
+                                         "window phasings"};
 
 int Ctx::query_ready(XpMode kind) {
   const char *noun = QUERY_NOUN[kind];
@@ -803,6 +804,218 @@ int Ctx::haplotype_dosages(int64_t n, const int32_t *indiv, int n_patterns, cons
     if (status) status[q] = stt;
     // (a restarted pass may have left an earlier attempt's numbers in a row that ended unresolved)
     if (stt != 0 && dosage) std::fill(dosage + (size_t)q * P, dosage + (size_t)(q + 1) * P, 0.0);
+  }
+  return HMC_OK;
+}
+
+int Ctx::window_group(const ExactArgs &x, const int32_t *ids, const std::vector<int32_t> &fm, int k, int dev_cu) {
+  QueryStats &qs = qstats[XP_WINDOW];
+  const int W = wn.W, K = wn.K, L = pan.L, ML = wn.maxlen;
+  const std::vector<int32_t> asked = asked_in(ids, k);
+  // device bytes of one individual: its rows' codes and probs, the two counts and the plan items of every window
+  const size_t cap = std::max<size_t>(1, WIN_OUT_BYTES / ((size_t)W * ((size_t)K * 12 + 8 + sizeof(WinItem))));
+  std::vector<WinItem> h_item;
+  std::vector<int32_t> h_code, h_cnt, h_ncfg;
+  std::vector<double> h_prob;
+  std::vector<uint8_t> xa(ML), xb(ML);
+  // sorted by the width their largest C needs: small individuals do not pay for wide ones
+  for (int nc : {4, 16, 64, 256, 1024}) {
+    std::vector<int32_t> sel;
+    for (int32_t bi : asked)
+      if (win_width(std::max(1, wn.maxc[wn.slot[bi]])) == nc) sel.push_back(bi);
+    if (sel.empty()) continue;
+    WindowArgs s;
+    s.n_windows = W;
+    s.k = K;
+    s.start = d_wn_start.p;
+    s.len = d_wn_len.p;
+    s.dig = d_wn_dig.p;
+    s.tier = wn_tier > 0 ? std::min(wn_tier, win_tier_max(nc)) : win_tier_max(nc);
+    s.lds_states = std::max(1, std::min(s.tier, x.fmax));  // no more LDS than the group's largest record asks for
+    // An individual past the tier gets a scratch slice of its own for its two frontiers at its widest window's
+    // stride (the kernel's: C + 1 made odd); a batch takes individuals while their slices fit the budget.
+    int spilled = 0;
+    std::vector<unsigned long long> need(sel.size(), 0), sbase;  // doubles
+    for (size_t u = 0; u < sel.size(); ++u) {
+      const int bi = sel[u];
+      if (fm[bi] <= s.tier) continue;
+      need[u] = 2ull * (unsigned)fm[bi] * (unsigned)((std::max(1, wn.maxc[wn.slot[bi]]) + 1) | 1);
+      if (need[u] * 8 > WIN_SCRATCH_BYTES)
+        return fail(HMC_ENOMEM, "window phasings: the frontiers of individual %d (%d states, %d configurations) need %llu bytes (scratch budget %llu)",
+                    i0 + bi, fm[bi], wn.maxc[wn.slot[bi]], need[u] * 8, (unsigned long long)WIN_SCRATCH_BYTES);
+      ++spilled;
+    }
+    qs.spilled += spilled;
+    qs.built = std::max(qs.built, nc);
+    const int rc = query_batches(
+        "exact_window_phasings", x, sel, d_wn_order, d_wn_status,
+        [&](size_t pos, int &nb) {
+          sbase.assign(1, 0);
+          while (pos + nb < sel.size() && (size_t)nb < cap && (nb == 0 || (sbase.back() + need[pos + nb]) * 8 <= WIN_SCRATCH_BYTES)) {
+            sbase.push_back(sbase.back() + need[pos + nb]);
+            ++nb;
+          }
+          return HMC_OK;
+        },
+        [&](const ExactArgs &xb_, size_t pos, int nb) {
+          const int grid = std::max(1, std::min(nb, dev_cu * 8));
+          hipError_t e;
+          if (spilled) {
+            if ((e = d_wn_scratch.ensure(std::max<size_t>(1, sbase.back()))) || (e = d_wn_sbase.ensure(sbase.size())) ||
+                (e = hipMemcpyAsync(d_wn_sbase.p, sbase.data(), sbase.size() * 8, hipMemcpyHostToDevice, st)))
+              return hipfail(e, "exact_window_phasings");
+            s.scratch = d_wn_scratch.p;
+            s.scratch_off = d_wn_sbase.p;
+          }
+          const size_t nw = (size_t)nb * W;
+          h_item.resize(nw);
+          for (int u = 0; u < nb; ++u)
+            std::copy(wn.item.begin() + (size_t)wn.slot[sel[pos + u]] * W, wn.item.begin() + ((size_t)wn.slot[sel[pos + u]] + 1) * W,
+                      h_item.begin() + (size_t)u * W);
+          if ((e = d_wn_item.ensure(nw)) || (e = d_wn_code.ensure(nw * K)) || (e = d_wn_prob.ensure(nw * K)) ||
+              (e = d_wn_count.ensure(nw)) || (e = d_wn_ncfg.ensure(nw)) ||
+              (e = hipMemcpyAsync(d_wn_item.p, h_item.data(), nw * sizeof(WinItem), hipMemcpyHostToDevice, st)) ||
+              (e = hipMemsetAsync(d_wn_code.p, 0xFF, nw * K * 4, st)) || (e = hipMemsetAsync(d_wn_prob.p, 0, nw * K * 8, st)) ||
+              (e = hipMemsetAsync(d_wn_count.p, 0, nw * 4, st)) || (e = hipMemsetAsync(d_wn_ncfg.p, 0, nw * 4, st)))
+            return hipfail(e, "exact_window_phasings");
+          s.item = d_wn_item.p;
+          s.code = d_wn_code.p;
+          s.prob = d_wn_prob.p;
+          s.count = d_wn_count.p;
+          s.n_config = d_wn_ncfg.p;
+          s.status = d_wn_status.p;
+          if (int rc2 = timed_sweep("exact_window_phasings", [&]() {
+                return (e = launch_exact_window_phasings(xb_, s, nc, grid, st)) ? hipfail(e, "exact_window_phasings") : HMC_OK;
+              }))
+            return rc2;
+          ++qs.batches;
+          h_code.resize(nw * K);
+          h_prob.resize(nw * K);
+          h_cnt.resize(nw);
+          h_ncfg.resize(nw);
+          if ((e = hipMemcpyAsync(h_code.data(), d_wn_code.p, nw * K * 4, hipMemcpyDeviceToHost, st)) ||
+              (e = hipMemcpyAsync(h_prob.data(), d_wn_prob.p, nw * K * 8, hipMemcpyDeviceToHost, st)) ||
+              (e = hipMemcpyAsync(h_cnt.data(), d_wn_count.p, nw * 4, hipMemcpyDeviceToHost, st)) ||
+              (e = hipMemcpyAsync(h_ncfg.data(), d_wn_ncfg.p, nw * 4, hipMemcpyDeviceToHost, st)))
+            return hipfail(e, "exact_window_phasings");
+          return (int)HMC_OK;
+        },
+        [&](int u, int64_t row, int64_t) {
+          // the rows the kernel found: codes to symbols (the rows past the count are written when the pass is over)
+          const int bi = qr.local(row), sl = wn.slot[bi];
+          const uint8_t *g0 = pan.idx.data() + ((size_t)(i0 + bi) * 2) * L, *g1 = g0 + L;
+          for (int w = 0; w < W; ++w) {
+            const size_t b = (size_t)u * W + w, o = (size_t)row * W + w;
+            const WinItem &it = wn.item[(size_t)sl * W + w];
+            const int c = std::max(0, std::min(h_cnt[b], K)), k0 = wn.start[w], len = wn.len[w];
+            wn.cnt[(size_t)sl * W + w] = c;
+            wn.ncfg[(size_t)sl * W + w] = h_ncfg[b];
+            for (int r = 0; r < c; ++r) {
+              if (wn.prob) wn.prob[o * K + r] = h_prob[b * K + r];
+              if (!wn.hap) continue;
+              const int code = h_code[b * K + r];
+              if (code < 0 || code >= it.C) continue;  // (the kernel writes none such)
+              win_spell(wn.dig.data() + it.dig0, it.nd, code, g0 + k0, g1 + k0, len, xa.data(), xb.data());
+              int32_t *h0 = wn.hap + ((o * K + r) * 2) * ML, *h1 = h0 + ML;
+              for (int l = 0; l < len; ++l) {
+                h0[l] = pan.symbol(k0 + l, xa[l]);
+                h1[l] = pan.symbol(k0 + l, xb[l]);
+              }
+            }
+          }
+          return hipSuccess;
+        });
+    if (rc) return rc;
+  }
+  return HMC_OK;
+}
+
+int Ctx::window_phasings(int64_t n, const int32_t *indiv, int n_windows, const int32_t *start, const int32_t *len, int maxlen, int k,
+                         int32_t *hap, double *prob, int32_t *count, int32_t *n_config, int32_t *status) {
+  int rc;
+  if ((rc = query_ready(XP_WINDOW))) return rc;
+  const int nl = nloc(), L = pan.L, W = n_windows, K = k;
+  if (W < 0 || (W > 0 && (!start || !len))) return fail(HMC_EARG, "window phasings: no windows given");
+  if (k < 1 || k > WIN_K_MAX) return fail(HMC_EARG, "window phasings: k = %d is outside [1, %d]", k, WIN_K_MAX);
+  if ((rc = query_rows(XP_WINDOW, n, indiv))) return rc;
+  for (int w = 0; w < W; ++w)
+    if (start[w] < 0 || len[w] < 1 || len[w] > maxlen || (long long)start[w] + len[w] > L)
+      return fail(HMC_EARG, "window phasings: window %d: start %d, length %d is outside [0, %d) or longer than maxlen %d", w, start[w],
+                  len[w], L, maxlen);
+  n = qr.size();
+  QueryStats &qs = qstats[XP_WINDOW];
+  qs = QueryStats();
+  if (n == 0 || W == 0) return HMC_OK;
+  // the plan: per asked individual and window its branching loci and C
+  const int cap = wn_cap > 0 ? wn_cap : WIN_CAP_MAX;
+  std::vector<uint8_t> nall(L);
+  for (int l = 0; l < L; ++l) nall[l] = (uint8_t)pan.sym[l].size();
+  wn.W = W;
+  wn.K = K;
+  wn.maxlen = maxlen;
+  wn.start = start;
+  wn.len = len;
+  wn.over_cap = 0;
+  wn.slot.assign(nl, -1);
+  int na = 0;
+  for (int i = 0; i < nl; ++i)
+    if (qr.asked[i]) wn.slot[i] = na++;
+  wn.item.assign((size_t)na * W, WinItem{0, 0, 0});
+  wn.dig.clear();
+  wn.maxc.assign(na, 0);
+  wn.cnt.assign((size_t)na * W, 0);
+  wn.ncfg.assign((size_t)na * W, 0);
+  for (int i = 0; i < nl; ++i) {
+    if (!qr.asked[i]) continue;
+    const uint8_t *g0 = pan.idx.data() + ((size_t)(i0 + i) * 2) * L, *g1 = g0 + L;
+    const int sl = wn.slot[i];
+    for (int w = 0; w < W; ++w) {
+      const size_t d0 = wn.dig.size();
+      const long long C = win_plan(g0 + start[w], g1 + start[w], nall.data() + start[w], len[w], cap, wn.dig);
+      WinItem &it = wn.item[(size_t)sl * W + w];
+      it.dig0 = (uint32_t)d0;
+      it.nd = (int32_t)(wn.dig.size() - d0);
+      it.C = C > cap ? 0 : (int32_t)C;
+      wn.over_cap += C > cap;
+      wn.maxc[sl] = std::max(wn.maxc[sl], it.C);
+    }
+  }
+  hipError_t er;
+  if ((er = d_xstatus.ensure(nl)) || (er = d_xre.ensure(nl)) || (er = d_xfmax.ensure(nl)) ||
+      (er = d_wn_dig.ensure(std::max<size_t>(1, wn.dig.size()))) || (er = d_wn_start.ensure(W)) || (er = d_wn_len.ensure(W)) ||
+      (!wn.dig.empty() &&
+       (er = hipMemcpyAsync(d_wn_dig.p, wn.dig.data(), wn.dig.size() * sizeof(WinDigit), hipMemcpyHostToDevice, st))) ||
+      (er = hipMemcpyAsync(d_wn_start.p, start, (size_t)W * 4, hipMemcpyHostToDevice, st)) ||
+      (er = hipMemcpyAsync(d_wn_len.p, len, (size_t)W * 4, hipMemcpyHostToDevice, st)) || (er = sync_st()))
+    return hipfail(er, "window phasings");
+  wn.hap = hap;
+  wn.prob = prob;
+  rc = xp_pass(XP_WINDOW, "window phasings", &qr.asked);
+  wn.hap = nullptr;
+  wn.prob = nullptr;
+  wn.start = wn.len = nullptr;
+  qs.constrained = wn.over_cap;
+  if (rc) return rc;
+  // statuses and counts; rows past the count (all of them at status 1, 2 or 4): the input genotype over the window
+  // at probability 0; -1 past the window's length
+  for (int64_t q = 0; q < n; ++q) {
+    const int i = qr.local(q), sl = wn.slot[i];
+    for (int w = 0; w < W; ++w) {
+      const size_t o = (size_t)q * W + w, pi = (size_t)sl * W + w;
+      const int stt = wn.item[pi].C == 0 ? 4 : qr.status[i], c = stt == 0 ? wn.cnt[pi] : 0;
+      if (status) status[o] = stt;
+      if (count) count[o] = c;
+      if (n_config) n_config[o] = stt == 0 ? wn.ncfg[pi] : 0;
+      for (int r = 0; r < K; ++r) {
+        if (prob && r >= c) prob[o * K + r] = 0.0;
+        if (!hap) continue;
+        for (int side = 0; side < 2; ++side) {
+          int32_t *h = hap + ((o * K + r) * 2 + side) * maxlen;
+          for (int l = 0; l < len[w] && r >= c; ++l) h[l] = pan.symbol(start[w] + l, pan.idx[((size_t)(i0 + i) * 2 + side) * L + start[w] + l]);
+          for (int l = len[w]; l < maxlen; ++l) h[l] = -1;
+        }
+      }
+    }
   }
   return HMC_OK;
 }

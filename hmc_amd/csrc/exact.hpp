@@ -3,6 +3,7 @@
 #pragma once
 #include "dosage_plan.hpp"
 #include "evidence_plan.hpp"
+#include "window_plan.hpp"
 #include "hmc_internal.hpp"
 
 namespace hmc {
@@ -297,5 +298,39 @@ constexpr unsigned long long rank_store_bytes(int kl, unsigned long long states,
 hipError_t launch_exact_state_totals(const ExactArgs &a, unsigned long long *total, hipStream_t st);
 // after exact_fb (forward only will do) over the same group; kl, block sizes 64 .. 256 and the grid do not change the bits
 hipError_t launch_exact_ranked_phasings(const ExactArgs &a, const RankArgs &s, int kl, int grid, hipStream_t st, int block = 256);
+
+// Window phasings (exact_window_phasings): the distinct haplotype pairs an
+// individual can carry over a window of loci, each with its exact posterior
+// summed over everything outside the window, ranked.  A state t carries one
+// double per ordered configuration of the window's branching loci seen so far
+// (window_plan.hpp: the code grows by a digit at each branching locus), an odd
+// number of doubles apart (the window's C rounded up) so that a wavefront's
+// reads of one code across states spread over the LDS banks.  item[q][w]: the digits and the count C of individual q of
+// the group (ExactArgs::order) and window w; C = 0 (over the cap) is skipped.
+// Rows: code[q][w][rank] (the row's a side is the smaller string), prob, and
+// per (q, w) the rows written and the configurations of positive posterior.
+// code is set to -1, prob, count, n_config and status to zero by the caller:
+// the kernel writes the rows it finds and the non-zero statuses only.
+struct WindowArgs {
+  int n_windows = 0, k = 0;
+  const int32_t *start = nullptr, *len = nullptr;  // [n_windows]
+  const WinItem *item = nullptr;                   // [n_order][n_windows]
+  const WinDigit *dig = nullptr;
+  int32_t *code = nullptr;                         // [n_order][n_windows][k]
+  double *prob = nullptr;                          // [n_order][n_windows][k]
+  int32_t *count = nullptr, *n_config = nullptr;   // [n_order][n_windows]
+  int32_t *status = nullptr;                       // [n_order] 0 ok, 1 unresolved, 2 P(genotype) subnormal
+  int tier = 0;                                    // an individual whose largest record has at most this many states sweeps in LDS
+  int lds_states = 0;                              // states the launch's LDS holds, 16 (NC + 1) B each
+  double *scratch = nullptr;                       // the frontiers of individuals past the tier: individual q's slice is
+  const unsigned long long *scratch_off = nullptr; // [scratch_off[q], scratch_off[q + 1]) doubles ([n_order + 1]; empty: none)
+};
+// Widths NC that are instantiated: the smallest that holds a batch's largest C runs it.
+constexpr int win_width(int c) { return c <= 4 ? 4 : c <= 16 ? 16 : c <= 64 ? 64 : c <= 256 ? 256 : 1024; }
+constexpr bool win_width_ok(int nc) { return nc == 4 || nc == 16 || nc == 64 || nc == 256 || nc == 1024; }
+// the states whose two frontiers 40 KiB of LDS hold beside the kernel's tables (about 21 KiB at NC = 1024)
+constexpr int win_tier_max(int nc) { return 40960 / (16 * (nc + 1)); }  // 512, 150, 39, 9, 2
+// after exact_fb over the same group; nc, block sizes 64 .. 256, the tier and the grid do not change the bits
+hipError_t launch_exact_window_phasings(const ExactArgs &a, const WindowArgs &s, int nc, int grid, hipStream_t st, int block = 256);
 
 }  // namespace hmc

@@ -222,6 +222,16 @@ struct PowScale {
     }
   }
   __device__ double term(double f, double b) const { return ldexp(f, sa) * ldexp(b, sb); }
+  // One label's sum by the calling wavefront, in label_sums' order: lane l adds
+  // term(g(t), bw[t]) over the states l, l + 64, ... ascending, then the fixed
+  // butterfly; every lane gets the sum.  No barrier.
+  template <class G>
+  __device__ double ordered_sum(int F, const double *bw, G g) const {
+    const int lane = threadIdx.x & (WAVE - 1);
+    double part[1] = {0.0};
+    for (int t = lane; t < F; t += WAVE) part[0] += term(g(t), bw[t]);
+    return group_sum_fixed<WAVE>(part);
+  }
   // The two-wave evaluation: wavefront 0 owns label 0, wavefront 1 label 1 (a
   // block of one wave takes both in turn); lane l adds term(g(t, label), bw[t])
   // over the states l, l + 64, ... ascending, then the fixed butterfly; lane 0

@@ -1492,4 +1492,227 @@ hipError_t launch_exact_ranked_phasings(const ExactArgs &a, const RankArgs &s, i
   return hipErrorInvalidValue;  // a width that is not built is an error, never another kernel
 }
 
+// Window phasings (hmc_window_phasings): for every window of a call the
+// distinct haplotype pairs the individual can carry over the window's loci,
+// each with its posterior summed over everything outside the window, the k
+// most probable in order.  The sum-product sibling of exact_ranked_phasings and
+// the discovering sibling of exact_haplotype_dosages: one block per individual,
+// one labelled forward sweep per window over the window's records only.  A
+// state t carries one double per ordered configuration c — the a-side and
+// b-side allele strings over the window's branching loci seen so far, as a
+// mixed-radix code (window_plan.hpp) that grows by a digit at each branching
+// locus, the first locus most significant.
+//   anchor    at the record of the window's first locus (a head record of
+//             head_len > 1 spells all of the window's head loci at once):
+//             g[c][t] = fwd[t] for the one c state t spells, 0 for the others;
+//   propagate record j from j - 1: c = (p, d), p the code so far and d the
+//             digit of locus j - 1 (no d at a fixed locus); where d is the
+//             digit t's own alleles spell, over t's contributions r in stored
+//             order g'[c][t] += g[rev(r) ? swap(p) : p][state(r)] * tpv[t], the
+//             first term assigns, later ones add; elsewhere 0.  swap, the code
+//             with the two sides exchanged, comes from a table in LDS that is
+//             rebuilt when the code grows;
+//   evaluate  at the record of the window's last locus: S_c = sum_t g[c][t]
+//             bwd[t], a wavefront per c in PowScale::label_sums' order;
+//   select    the row of the unordered pair {x, y} is the orientation with the
+//             smaller code (its a side is the smaller string); prob = (S_c +
+//             S_swap(c)) / P(genotype), S_c / P(genotype) when c = swap(c).
+//             Row c's rank is the number of rows that precede it — larger prob,
+//             or equal prob and the smaller (a string, b string) — counted by
+//             one thread per row, so nothing about the launch enters; ranks
+//             below k are written.
+// These are exact_haplotype_dosages' operations for the two-sided pattern the
+// row spells: its g[0] is g[c], its g[1] is g[swap(c)], and the terms it adds
+// beyond these are exact zeros.  So a row's prob is that call's double (half of
+// it when the two strings are equal), and depends on the records, the forward
+// and backward values and the window alone: NC, the other windows, k, block
+// size, grid, grouping, shard and tier do not change the bits.  No
+// floating-point atomics, no cross-wave sums beyond S_c + S_swap(c).
+// A state's configurations lie an odd number of doubles (the window's C rounded
+// up) apart from the next state's, so the lanes of an evaluating wavefront
+// (consecutive states, one c) and of a propagating one (one state, consecutive
+// c) both spread over the LDS banks.  The two frontiers of a window live in LDS
+// when its largest record's fit there at that stride — always when the
+// individual's largest record has at most `tier` states — else in the
+// individual's slice of an HBM scratch: the same doubles in the same order.
+// EXT (ExactArgs::extended): as exact_haplotype_dosages.
+template <int NC, bool EXT>
+__global__ __launch_bounds__(256) void exact_window_phasings(ExactArgs a, WindowArgs s) {
+  extern __shared__ __attribute__((aligned(16))) double wn_lds[];  // 2 (NC + 1) lds_states doubles: a window's two frontiers
+  constexpr int NCS = NC + 1;
+  __shared__ double s_sum[NC], s_prob[NC];  // S_c; the rows' probs
+  __shared__ uint16_t s_swp[NC], s_list[NC];  // swap of the codes so far; the rows of positive prob
+  __shared__ WinDigit s_dig[WIN_DIGITS_MAX];
+  __shared__ int s_n, s_f;  // rows of positive prob; the window's largest record
+  const int tid = threadIdx.x, NT = blockDim.x, lane = tid & (WAVE - 1), wave = tid / WAVE, nw = NT / WAVE;
+  const int L = a.L, hl = a.head_len, W = s.n_windows, K = s.k;
+  for (int q = blockIdx.x; q < a.n_order; q += gridDim.x) {
+    const QueryInd<EXT> ind(a, q);
+    const int gu = ind.give_up_status();
+    // (the individual's largest record against the tier; the windows place their own frontiers below)
+    FrontierStore fr(a, ind.roff, ind.resolved(), wn_lds, min(s.tier, s.lds_states), s.lds_states, s.scratch, 0x7FFFFFFF, NCS);
+    const unsigned long long sc0 = s.scratch ? s.scratch_off[q] : 0ull, sc1 = s.scratch ? s.scratch_off[q + 1] : 0ull;
+    if (gu || !fr.fits) {  // no rows: the caller's zeros stand
+      if (tid == 0) s.status[q] = fr.fits ? gu : 1;
+      continue;
+    }
+    PowScale<EXT> ps(ind);
+    for (int w = 0; w < W; ++w) {
+      const WinItem it = s.item[(size_t)q * W + w];
+      const int k0 = s.start[w], k1 = k0 + s.len[w];
+      if (it.C < 1 || it.C > NC || it.nd < 0 || it.nd > WIN_DIGITS_MAX || k0 < 0 || k1 <= k0 || k1 > L) continue;  // over the cap
+      __syncthreads();  // the previous window's last readers of the tables and the frontiers are done
+      if (tid < it.nd) s_dig[tid] = s.dig[it.dig0 + tid];
+      if (tid == 0) s_n = s_f = 0;
+      __syncthreads();
+      int j = k0 < hl ? hl : k0 + 1;               // the record `cur` belongs to
+      const int jl = k1 - 1 < hl ? hl : k1;        // the record of the window's last locus
+      const bool head = j == hl && hl > 1;         // the window's loci below head_len, from the head patterns
+      const int ka = head ? min(k1, hl) : k0 + 1;  // the anchor spells the loci [k0, ka)
+      int m = 0, cc = 1;                           // digits in the code so far, and its range (block-uniform)
+      while (m < it.nd && s_dig[m].rel < ka - k0) cc *= win_radix(s_dig[m++]);
+      if (cc > NC) continue;  // (the host builds none such)
+      // The window's own stride and store: its C rounded up to an odd count of doubles per state, and LDS when
+      // its largest record's two frontiers fit there at that stride, else the individual's slice of the scratch —
+      // a narrow window of a wide individual neither strides nor spills like its widest one.
+      const int ncs = (it.C + 1) | 1;
+      for (int r = j + tid; r <= jl; r += NT) atomicMax(&s_f, ind.F(r));
+      __syncthreads();
+      const size_t fwin = (size_t)s_f, need = 2 * fwin * ncs;
+      const bool in_lds = need <= (size_t)2 * NCS * s.lds_states;
+      if (!in_lds && need > sc1 - sc0) continue;  // (none such: the host sizes the slice from the largest record and C)
+      double *cur = in_lds ? wn_lds : s.scratch + sc0, *prev = cur + fwin * ncs;
+      {
+        const RecView R = ind.rec(j);
+        const double *fw = ind.fwd(j);
+        for (int t = tid; t < R.F; t += NT) {
+          int code = 0;
+          for (int i = 0; i < m && code >= 0; ++i) {
+            uint32_t xa, xb;
+            state_alleles(a, R, head, k0 + s_dig[i].rel, t, xa, xb);
+            const int d = win_encode(s_dig[i], xa, xb);
+            code = d < 0 ? -1 : code * win_radix(s_dig[i]) + d;
+          }
+          double *g = cur + (size_t)t * ncs;
+          for (int c = 0; c < cc; ++c) g[c] = 0.0;
+          if (code >= 0) g[code] = fw[t];
+        }
+      }
+      for (int c = tid; c < cc; c += NT) s_swp[c] = (uint16_t)win_swap_code(s_dig, m, c);
+      __syncthreads();
+      while (j < jl) {  // record j + 1 from record j (j + 1 > head_len: never the head record)
+        ++j;
+        {
+          double *x = prev;
+          prev = cur;
+          cur = x;
+        }
+        const RecView R = ind.rec(j);
+        const int step = EXT ? ind.spare(j)[0] - ind.spare(j - 1)[0] : 0;
+        const bool br = m < it.nd && s_dig[m].rel == j - 1 - k0;  // locus j - 1 branches: the code takes its digit
+        const WinDigit dg = s_dig[br ? m : 0];
+        const int rad = br ? win_radix(dg) : 1, cn = cc * rad;
+        if (cn > NC) break;  // (none such)
+        int sh = 0;  // items (t, p) by a power of two that holds the new range
+        while ((1 << sh) < cn) ++sh;
+        const int items = R.F << sh;
+        for (int idx = tid; idx < items; idx += NT) {
+          const int t = idx >> sh, p = idx & ((1 << sh) - 1);
+          if (p >= cn) continue;
+          int pp = p;
+          bool on = true;
+          if (br) {
+            const uint32_t h = R.hdr[t];
+            pp = p / rad;
+            on = p - pp * rad == win_encode(dg, h & 0xFFu, (h >> 8) & 0xFFu);
+          }
+          double v = 0.0;
+          if (on) {
+            const double tpv = R.tpv[t];
+            const int sp = s_swp[pp];
+            const uint32_t r0 = R.cb[t], r1 = R.cb[t + 1];
+            for (uint32_t r = r0; r < r1; ++r) {
+              const uint32_t cw = R.ct[r];
+              const double x = prev[(size_t)cw_state(cw) * ncs + (cw_rev(cw) ? sp : pp)] * tpv;
+              v = r == r0 ? x : v + x;
+            }
+            if (EXT) v = ldexp(v, step);
+          }
+          cur[(size_t)t * ncs + p] = v;
+        }
+        __syncthreads();
+        if (br) {
+          ++m;
+          cc = cn;
+          for (int c = tid; c < cc; c += NT) s_swp[c] = (uint16_t)win_swap_code(s_dig, m, c);
+          __syncthreads();
+        }
+      }
+      if (j != jl || m != it.nd) continue;  // (none such)
+      {
+        const RecView R = ind.rec(j);
+        const double *bw = ind.bwd(j);
+        ps.at_record(ind, ind.spare(j));
+        for (int c = wave; c < cc; c += nw) {  // wave-uniform
+          const double v = ps.ordered_sum(R.F, bw, [&](int t) { return cur[(size_t)t * ncs + c]; });
+          if (lane == 0) s_sum[c] = v;
+        }
+      }
+      __syncthreads();
+      for (int c = tid; c < cc; c += NT) {
+        const int sc = s_swp[c];
+        if (c > sc) continue;  // the other orientation spells the row
+        const double pr = c == sc ? s_sum[c] / ps.pgs : (s_sum[c] + s_sum[sc]) / ps.pgs;
+        s_prob[c] = pr;
+        if (pr > 0.0) s_list[atomicAdd(&s_n, 1)] = (uint16_t)c;  // (the list's order does not enter a rank)
+      }
+      __syncthreads();
+      const int n = s_n;
+      const size_t base = (size_t)q * W + w;
+      for (int i = tid; i < n; i += NT) {
+        const int c = s_list[i];
+        const double pc = s_prob[c];
+        int rank = 0;
+        for (int u = 0; u < n; ++u) {
+          const int d = s_list[u];
+          const double pd = s_prob[d];
+          if (pd > pc || (pd == pc && d != c && win_order_less(s_dig, m, d, c))) ++rank;
+        }
+        if (rank < K) {
+          s.code[base * K + rank] = c;
+          s.prob[base * K + rank] = pc;
+        }
+      }
+      if (tid == 0) {
+        s.count[base] = min(n, K);
+        s.n_config[base] = n;
+      }
+    }
+  }
+}
+
+template <int NC>
+static hipError_t launch_window(const ExactArgs &a, const WindowArgs &s, int grid, hipStream_t st, int block) {
+  const size_t lds = (size_t)s.lds_states * 16 * (NC + 1);
+  if (a.extended) hipLaunchKernelGGL((exact_window_phasings<NC, true>), dim3(grid), dim3(block), lds, st, a, s);
+  else hipLaunchKernelGGL((exact_window_phasings<NC, false>), dim3(grid), dim3(block), lds, st, a, s);
+  return hipGetLastError();
+}
+
+hipError_t launch_exact_window_phasings(const ExactArgs &a, const WindowArgs &s, int nc, int grid, hipStream_t st, int block) {
+  if (a.n_order <= 0 || s.n_windows <= 0) return hipSuccess;
+  if (block < WAVE || block > 256 || block % WAVE || grid < 1 || !win_width_ok(nc) || s.k < 1 || s.k > WIN_K_MAX || s.tier < 1 ||
+      s.lds_states < 1 || s.lds_states > win_tier_max(nc) || !s.start || !s.len || !s.item || !s.dig || !s.code || !s.prob ||
+      !s.count || !s.n_config || !s.status || (s.scratch && !s.scratch_off))
+    return hipErrorInvalidValue;
+  switch (nc) {
+    case 4: return launch_window<4>(a, s, grid, st, block);
+    case 16: return launch_window<16>(a, s, grid, st, block);
+    case 64: return launch_window<64>(a, s, grid, st, block);
+    case 256: return launch_window<256>(a, s, grid, st, block);
+    case 1024: return launch_window<1024>(a, s, grid, st, block);
+  }
+  return hipErrorInvalidValue;  // a width that is not built is an error, never another kernel
+}
+
 }  // namespace hmc

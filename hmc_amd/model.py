@@ -823,6 +823,63 @@ class HaploModel:
         """ranked_phasings of the whole shard as text, one line per individual and rank (hmc_write_ranked_phasings)."""
         self._check(lib().hmc_write_ranked_phasings(self._h, path.encode(), int(k)))
 
+    def window_phasings(self, start, length, k: int, indiv=None) -> dict:
+        """The distinct haplotype pairs an individual can carry over each
+        window start[w] .. start[w] + length[w] - 1, each with its exact
+        posterior summed over everything outside the window, the k most
+        probable in order (hmc_window_phasings; 1 <= k <= 1024).  For the panel
+        indices `indiv` (any order, repeats allowed; None = this rank's whole
+        shard): hap[n, W, k, 2, maxlen] symbols (-1 past a window's length;
+        hap[..., 0, :] the lexicographically smaller string), prob[n, W, k]
+        descending, count[n, W] rows that are real, n_config[n, W] pairs of
+        positive posterior, status[n, W] (0 ok; 1, 2 as map_phase; 4 the
+        window's ordered configurations exceed the cap).  Rows at and past
+        count carry the input genotype over the window at prob 0.  A row's
+        prob is haplotype_dosages' double for the two-sided pattern the row
+        spells (half of it when the two strings are equal)."""
+        st = np.ascontiguousarray(start, np.int32).reshape(-1)
+        ln = np.ascontiguousarray(length, np.int32).reshape(-1)
+        if len(st) != len(ln):
+            raise ValueError("start and length differ in length")
+        if indiv is None:
+            qi, n = None, self.i1 - self.i0
+        else:
+            qi = np.ascontiguousarray(indiv, np.int32).reshape(-1)
+            n = len(qi)
+        W, kk = len(st), max(int(k), 0)
+        maxlen = max(1, int(ln.max())) if W else 1
+        out = dict(hap=np.zeros((n, W, kk, 2, maxlen), np.int32), prob=np.zeros((n, W, kk), np.float64),
+                   count=np.zeros((n, W), np.int32), n_config=np.zeros((n, W), np.int32), status=np.zeros((n, W), np.int32))
+        self._check(lib().hmc_window_phasings(self._h, n, None if qi is None else _p(qi, C.c_int32), W, _p(st, C.c_int32),
+                                              _p(ln, C.c_int32), maxlen, int(k), _p(out["hap"], C.c_int32),
+                                              _p(out["prob"], C.c_double), _p(out["count"], C.c_int32),
+                                              _p(out["n_config"], C.c_int32), _p(out["status"], C.c_int32)))
+        return out
+
+    def window_stats(self) -> dict:
+        """Device ms and counts of the last window_phasings (hmc_last_window_stats)."""
+        s, f, k = C.c_double(), C.c_double(), C.c_double()
+        g, p, sp, b, oc = C.c_int(), C.c_int(), C.c_int(), C.c_int(), C.c_int()
+        self._check(lib().hmc_last_window_stats(self._h, C.byref(s), C.byref(f), C.byref(k), C.byref(g), C.byref(p),
+                                                C.byref(sp), C.byref(b), C.byref(oc)))
+        return dict(structure_ms=s.value, fb_ms=f.value, sweep_ms=k.value, groups=g.value, n_pruned=p.value,
+                    n_spilled=sp.value, configs_built=b.value, n_over_cap=oc.value)
+
+    def set_window_tuning(self, max_configs: int = 0, tier: int = 0):
+        """Cap on a window's ordered configurations (at most 1024) and states
+        per locus the window sweep keeps in LDS; 0 = default for each.  Results
+        do not depend on it, status 4 aside."""
+        self._check(lib().hmc_set_window_tuning(self._h, int(max_configs), int(tier)))
+
+    def write_window_phasings(self, path: str, start, length, k: int = 8):
+        """window_phasings of the whole shard as text, one line per individual of status 0, window and rank
+        (hmc_write_window_phasings)."""
+        st = np.ascontiguousarray(start, np.int32).reshape(-1)
+        ln = np.ascontiguousarray(length, np.int32).reshape(-1)
+        if len(st) != len(ln):
+            raise ValueError("start and length differ in length")
+        self._check(lib().hmc_write_window_phasings(self._h, path.encode(), len(st), _p(st, C.c_int32), _p(ln, C.c_int32), int(k)))
+
     def set_posterior_range(self, extended: bool):
         """Range of genotype_posteriors, switch_posteriors, pair_posteriors,
         posterior_draws and their write_* forms (hmc_set_posterior_range).

@@ -742,6 +742,81 @@ int hmc_ranked_phasings(hmc_ctx *ctx, int64_t n, const int32_t *indiv, int k, in
  * reference interface. */
 int hmc_last_ranked_stats(const hmc_ctx *ctx, double *structure_ms, double *fb_ms, double *sweep_ms, int *groups,
                           int *n_pruned, int *k_built);
+/* Window phasings: for every individual asked for and every window of loci,
+ * the distinct haplotype pairs the individual can carry over the window, each
+ * with its exact posterior summed over everything outside the window, the k
+ * most probable in order — the diplotype call of a gene-sized window.  The
+ * sum-product sibling of hmc_ranked_phasings (whose whole-panel pairs all have
+ * vanishing posteriors on long panels) and the discovering sibling of
+ * hmc_haplotype_dosages (which prices patterns the caller already knows).
+ * indiv[n] as for hmc_map_phase: panel indices inside this rank's shard, any
+ * order, repeats allowed, NULL = the whole shard.  Windows start[w], len[w]
+ * (1 <= len[w] <= maxlen, inside [0, L)) may overlap, repeat and come in any
+ * order; one call runs one structure pass and one forward-backward pass over
+ * the individuals asked for and serves every window from them.  1 <= k <= 1024.
+ * Outputs, any of which may be NULL: hap[n][n_windows][k][2][maxlen] allele
+ * symbols (-1 past len[w]), prob[n][n_windows][k], count[n][n_windows] rows
+ * that are real, n_config[n][n_windows] pairs of positive computed posterior,
+ * status[n][n_windows].
+ * Configurations.  A locus of the window is fixed for an individual when both
+ * input alleles are present and equal, else branching.  An ordered
+ * configuration is the pair of allele strings (a side, b side) over the
+ * branching loci; there are C = the product over them of 2 (heterozygous),
+ * 2 A - 1 (one allele missing) or A^2 (both missing), A the locus's alleles
+ * (hmc_allele_table).  C above the cap (1 024; hmc_set_window_tuning lowers
+ * it) is status 4 — whatever the individual's own status — with the input
+ * genotype over the window at prob 0, count 0 and n_config 0.  Status 0, 1, 2
+ * as for hmc_map_phase; rows of status 1 and 2 likewise.
+ * Rows.  A row spells an unordered window pair {x, y} once, hap[..][0] the
+ * lexicographically smaller string by allele-table index; prob = the sum of
+ * post({h0, h1}) over the whole-panel unordered pairs whose restriction to
+ * the window is {x, y}, post the posterior hmc_posterior_draws samples.  Rows
+ * by prob descending, then by (hap[0] indices, hap[1] indices) ascending; the
+ * first k of prob > 0 are the rows, count = min(k, n_config); rows past count
+ * carry the input genotype over the window at prob 0.  Row r has the same
+ * bytes for every k > r.
+ * Arithmetic.  prob is the very double hmc_haplotype_dosages returns for that
+ * individual and the two-sided pattern (start[w], len[w], A = hap[0], B =
+ * hap[1]), in both ranges — exactly half of it when hap[0] = hap[1], where
+ * the dosage counts both orientations.  In full: at the window's first record
+ * every state's forward value goes to the one ordered configuration the state
+ * spells there (a head record of head_len > 1 spells all of the window's head
+ * loci at once) and every other configuration gets 0; per record above it each
+ * (state t, configuration) takes the running sum over t's contributions in
+ * stored order of (previous value x tpv[t]), a reversed link taking the
+ * side-swapped configuration, the first term assigning and later ones adding,
+ * extended range multiplying by the record's exponent step; at the window's
+ * last record S_c is the ordered sum against the backward values (lane l adds
+ * states l, l + 64, ..., then the fixed butterfly) and prob = (S_c +
+ * S_swap(c)) / P(genotype) with one addition and one division, S_c /
+ * P(genotype) when c = swap(c).  A row's bits depend on the model, the range,
+ * the individual and its own (start, len): not on the other windows or
+ * individuals, k, the cap, the configuration width the kernel was built with,
+ * the tier, launch shapes, batches, groups or sharding.
+ * For an individual with a missing allele at a head locus, window loci below
+ * head_len come from the reference's head pairing, which is not a phasing
+ * model: for a window that touches them only the normalisation holds.
+ * Needs a preceding hmc_resolve_all (any E-step mode) and changes no later
+ * result.  n = 0 or n_windows = 0 is HMC_OK with no device work and zeroed
+ * stats.  HMC_EARG, with a message naming the first offender, for a window
+ * with start < 0, len < 1, len > maxlen or start + len > L, k outside
+ * [1, 1024], an individual outside this rank's shard, no E-step or a model
+ * changed since the last one; HMC_EUNSUPPORTED as for
+ * hmc_genotype_posteriors; HMC_ENOMEM, naming the individual, when one
+ * individual's two frontiers at the configuration width it needs exceed the
+ * 4 GiB scratch budget.  Replaces no reference interface. */
+int hmc_window_phasings(hmc_ctx *ctx, int64_t n, const int32_t *indiv, int n_windows, const int32_t *start,
+                        const int32_t *len, int maxlen, int k, int32_t *hap, double *prob, int32_t *count,
+                        int32_t *n_config, int32_t *status);
+/* Last hmc_window_phasings: device ms of its structure passes, of the
+ * forward-backward kernel and of the window sweeps; groups; individuals on
+ * pruned records; individuals whose frontiers went through the device-memory
+ * scratch; the widest configuration width NC that ran (4, 16, 64, 256 or
+ * 1 024: a group's individuals run sorted by the width their largest C needs,
+ * one width per launch); (individual, window) pairs over the cap.  Replaces no
+ * reference interface. */
+int hmc_last_window_stats(const hmc_ctx *ctx, double *structure_ms, double *fb_ms, double *sweep_ms, int *groups,
+                          int *n_pruned, int *n_spilled, int *configs_built, int *n_over_cap);
 /* Range of the posterior family (hmc_genotype_posteriors, hmc_switch_posteriors,
  * hmc_pair_posteriors, hmc_posterior_draws, hmc_map_phase,
  * hmc_ranked_phasings and their hmc_write_* forms).
@@ -946,7 +1021,27 @@ int hmc_write_ranked_phasings(hmc_ctx *ctx, const char *path, int k);
 int hmc_write_haplotype_dosages(hmc_ctx *ctx, const char *path, int n_patterns, const char *const *names,
                                 const int32_t *start, const int32_t *len, int maxlen, const int32_t *alleles_a,
                                 const int32_t *alleles_b);
+/* hmc_window_phasings of the whole shard as text (hmc_resolve --output-windows
+ * FILE --windows WINFILE --window-k K): the header
+ * "Id\tWindow\tStart\tLength\tRank\tPosterior\tHaplotype0\tHaplotype1", then one
+ * line per individual, window (its index in the call) and rank < count of
+ * status 0, individual-major: the posterior as %.17g (reads back to the same
+ * double) and the two haplotypes over the window's loci, spelled as
+ * hmc_write_posterior_draws spells them.  Windows and errors as for
+ * hmc_window_phasings.  Needs a preceding hmc_resolve_all or hmc_run.
+ * Replaces no reference interface. */
+int hmc_write_window_phasings(hmc_ctx *ctx, const char *path, int n_windows, const int32_t *start, const int32_t *len,
+                              int k);
 /* ---- tuning -------------------------------------------------------------- */
+/* hmc_window_phasings, 0 = default for each.  max_configs: the cap on a
+ * window's ordered configurations C (at most 1 024), above which an
+ * (individual, window) pair is status 4.  tier_states: states per locus whose
+ * frontiers the sweep keeps in LDS (16 (NC + 1) bytes per state; default and
+ * most: 512, 150, 39, 9, 2 at NC = 4 .. 1 024); an individual with a larger
+ * frontier keeps the windows that do not fit the LDS in a device-memory scratch.  HMC_EARG outside [0, 1024]
+ * and [0, 512].  Results do not depend on it, status 4 aside.  Replaces no
+ * reference interface. */
+int hmc_set_window_tuning(hmc_ctx *ctx, int max_configs, int tier_states);
 /* frontier_cap: initial states per locus and individual (doubles on
  * overflow, at most 2 097 151); trace_bytes: trace-store budget (0 =
  * automatic); waves: resident E-step waves (0 = automatic). */

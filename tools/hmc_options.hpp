@@ -30,7 +30,11 @@ struct Options {
   std::string output_ranked;           // --output-ranked FILE
   int ranked = 4;                      // --ranked K (1 .. 16)
   bool have_ranked = false;
-  bool extended_range = false;         // --extended-range (needs one of the --output-*posteriors / --output-draws / --output-dosages / --output-map / --output-ranked options)
+  std::string output_windows;          // --output-windows FILE
+  std::string windows;                 // --windows WINFILE (required with it)
+  int window_k = 8;                    // --window-k K (1 .. 1024)
+  bool have_window_k = false;
+  bool extended_range = false;         // --extended-range (needs one of the --output-*posteriors / --output-draws / --output-dosages / --output-map / --output-ranked / --output-windows options)
 };
 
 // --output-posteriors (no reference counterpart): <first file>.posteriors, the
@@ -74,7 +78,11 @@ constexpr const char *USAGE =
     "  --output-ranked FILE [--ranked K]  write FILE: for every individual the K most probable haplotype\n"
     "                        pairs under the final model, each once, in order, with their posteriors\n"
     "                        (default K = 4, at most 16; an exact ranking, no k-best cut)\n"
-    "  --extended-range      the eight options above in extended range: individuals whose likelihood\n"
+    "  --output-windows FILE --windows WINFILE [--window-k K]  write FILE: for every individual and every\n"
+    "                        window of WINFILE (lines: name start len, start the 0-based first locus) the K\n"
+    "                        most probable haplotype pairs over the window's loci, each with its posterior\n"
+    "                        summed over everything outside the window (default K = 8, at most 1024)\n"
+    "  --extended-range      the nine options above in extended range: individuals whose likelihood\n"
     "                        underflows a double (panels of more than about 1 200 loci) get lines too";
 
 // 0 on success; otherwise `err` says what is wrong (a missing value, an
@@ -114,6 +122,9 @@ inline int parse_options(int argc, const char *const *argv, Options &o, std::str
     else if (a == "--evidence") { if (!next()) return 1; o.evidence = v; }
     else if (a == "--output-ranked") { if (!next()) return 1; o.output_ranked = v; }
     else if (a == "--ranked") { if (!next()) return 1; o.ranked = atoi(v); o.have_ranked = true; }
+    else if (a == "--output-windows") { if (!next()) return 1; o.output_windows = v; }
+    else if (a == "--windows") { if (!next()) return 1; o.windows = v; }
+    else if (a == "--window-k") { if (!next()) return 1; o.window_k = atoi(v); o.have_window_k = true; }
     else if (a == "--haplotypes") { if (!next()) return 1; o.haplotypes = v; }
     else if (a == "--extended-range") o.extended_range = true;
     else if (a == "--seed") { if (!next()) return 1; o.seed = strtoull(v, nullptr, 10); o.have_seed = true; }
@@ -159,10 +170,22 @@ inline int parse_options(int argc, const char *const *argv, Options &o, std::str
     err = "--ranked needs --output-ranked FILE\n" + std::string(USAGE);
     return 1;
   }
+  if (o.output_windows.empty() != o.windows.empty()) {
+    err = "--output-windows FILE and --windows WINFILE need each other\n" + std::string(USAGE);
+    return 1;
+  }
+  if (!o.output_windows.empty() && (o.window_k < 1 || o.window_k > 1024)) {
+    err = "--output-windows needs --window-k K with 1 <= K <= 1024\n" + std::string(USAGE);
+    return 1;
+  }
+  if (o.have_window_k && o.output_windows.empty()) {
+    err = "--window-k needs --output-windows FILE\n" + std::string(USAGE);
+    return 1;
+  }
   if (o.extended_range && !o.output_posteriors && !o.output_switch_posteriors && o.output_pair_posteriors.empty() &&
       o.output_draws.empty() && o.output_dosages.empty() && o.output_map.empty() && o.output_map_given.empty() &&
-      o.output_ranked.empty()) {
-    err = "--extended-range needs --output-posteriors, --output-switch-posteriors, --output-pair-posteriors, --output-draws, --output-dosages, --output-map, --output-map-given or --output-ranked\n" +
+      o.output_ranked.empty() && o.output_windows.empty()) {
+    err = "--extended-range needs --output-posteriors, --output-switch-posteriors, --output-pair-posteriors, --output-draws, --output-dosages, --output-map, --output-map-given, --output-ranked or --output-windows\n" +
           std::string(USAGE);
     return 1;
   }

@@ -15,7 +15,8 @@
 //               [--output-draws FILE [--draws 100] [--seed 0]]
 //               [--output-dosages FILE --haplotypes HAPFILE] [--output-map FILE]
 //               [--output-map-given FILE --evidence EVFILE]
-//               [--output-ranked FILE [--ranked 4]] [--extended-range] [--device 0] datafile ...
+//               [--output-ranked FILE [--ranked 4]]
+//               [--output-windows FILE --windows WINFILE [--window-k 8]] [--extended-range] [--device 0] datafile ...
 // --output-posteriors (no reference counterpart) writes <first file>.posteriors:
 // genotype posteriors at the loci with a missing input allele, under the final
 // model (hmc_write_posteriors).  --output-switch-posteriors (none either)
@@ -40,7 +41,12 @@
 // --output-ranked FILE [--ranked K] (none either) writes FILE: every
 // individual's K most probable haplotype pairs under the final model, each
 // once, in order, with their posteriors (hmc_write_ranked_phasings).
-// --extended-range (none either) runs those eight in extended range
+// --output-windows FILE --windows WINFILE [--window-k K] (none either) writes
+// FILE: for every individual and every window listed in WINFILE
+// (hmc_winfile.hpp) the K most probable haplotype pairs over the window's loci,
+// each with its posterior summed over everything outside the window
+// (hmc_write_window_phasings); the Window column is the window's place in WINFILE, from 0.
+// --extended-range (none either) runs those nine in extended range
 // (hmc_set_posterior_range): individuals whose likelihood underflows a double
 // get lines too.
 #include <cstdio>
@@ -53,6 +59,7 @@
 #include "../include/hmc_amd.h"
 #include "hmc_hapfile.hpp"
 #include "hmc_options.hpp"
+#include "hmc_winfile.hpp"
 
 int main(int argc, char **argv) {
   hmc_cli::Options o;
@@ -100,6 +107,21 @@ int main(int argc, char **argv) {
     }
     if (hmc_cli::parse_hapfile(hf, types, haps, herr)) {
       fprintf(stderr, "%s\n", herr.c_str());
+      hmc_ctx_destroy(ctx);
+      return 1;
+    }
+  }
+  hmc_cli::WinList wins;
+  if (!o.windows.empty()) {  // read before the run: a malformed list fails at once
+    std::string werr;
+    std::ifstream wf(o.windows);
+    if (!wf) {
+      fprintf(stderr, "Can not open file %s!\n", o.windows.c_str());
+      hmc_ctx_destroy(ctx);
+      return 1;
+    }
+    if (hmc_cli::parse_winfile(wf, L, wins, werr)) {
+      fprintf(stderr, "%s\n", werr.c_str());
       hmc_ctx_destroy(ctx);
       return 1;
     }
@@ -174,6 +196,11 @@ int main(int argc, char **argv) {
   }
   if (!o.output_ranked.empty()) {  // of the same E-step
     if ((rc = hmc_write_ranked_phasings(ctx, o.output_ranked.c_str(), o.ranked))) die("hmc_write_ranked_phasings");
+  }
+  if (!o.output_windows.empty()) {  // of the same E-step
+    if ((rc = hmc_write_window_phasings(ctx, o.output_windows.c_str(), (int)wins.names.size(), wins.start.data(), wins.len.data(),
+                                        o.window_k)))
+      die("hmc_write_window_phasings");
   }
   hmc_ctx_destroy(ctx);
   return 0;
