@@ -61,6 +61,8 @@ _SIGS = [
                               _P(C.c_int32), _i]),
     ("hmc_set_patterns", _i, [_vp, _i, _P(C.c_int32), _P(C.c_int32), _P(_d), _P(_d), _P(C.c_int32),
                               _P(C.c_int32)]),
+    ("hmc_set_patterns_spelled", _i, [_vp, _i, _P(C.c_int32), _P(C.c_int32), _P(C.c_int32), _i, _P(_d), _P(_d), _P(_d),
+                                      _P(C.c_int32)]),
     ("hmc_resolve_all", _i, [_vp, _P(_d), _P(_i), _P(_u64)]),
     ("hmc_get_estep", _i, [_vp, _P(_d), _P(C.c_int32), _P(C.c_int32), _P(_d), _P(_d), _P(_d)]),
     ("hmc_get_estep_stats", _i, [_vp, _P(C.c_int32)]),

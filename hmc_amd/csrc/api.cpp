@@ -791,6 +791,37 @@ int hmc_set_patterns(hmc_ctx *h, int P, const int32_t *start, const int32_t *len
   return HMC_OK;
 }
 
+int hmc_set_patterns_spelled(hmc_ctx *h, int P, const int32_t *start, const int32_t *len, const int32_t *alleles,
+                             int maxlen, const double *freq, const double *prefix, const double *tp,
+                             const int32_t *succ) {
+  if (!h || !h->c.have_panel || P <= 0 || maxlen <= 0 || !start || !len || !alleles || !freq || !prefix || !tp || !succ)
+    return HMC_EARG;
+  Ctx &c = h->c;
+  const int A = c.pan.amax, L = c.pan.L;
+  Ctx::Cands t;
+  std::vector<uint8_t> al;
+  for (int i = 0; i < P; ++i) {
+    if (start[i] < 0 || len[i] <= 0 || len[i] > maxlen || start[i] + len[i] > L)
+      return c.fail(HMC_EARG, "pattern %d: start %d, length %d", i, start[i], len[i]);
+    al.resize(len[i]);
+    for (int q = 0; q < len[i]; ++q) {
+      const int j = c.pan.index_of(start[i] + q, alleles[(size_t)i * maxlen + q]);
+      if (j < 0) return c.fail(HMC_EARG, "pattern %d: allele not in locus table", i);
+      al[q] = (uint8_t)j;
+    }
+    t.push(start[i], len[i], al.data(), 0, false, freq[i], prefix[i], tp[i]);
+  }
+  std::vector<int32_t> su((size_t)P * A);
+  for (size_t i = 0; i < su.size(); ++i) {
+    if (succ[i] >= P) return c.fail(HMC_EARG, "successor %d of %d patterns", succ[i], P);
+    su[i] = succ[i] < 0 ? -1 : succ[i];
+  }
+  c.head_len = std::max(c.min_len, 1);
+  // the way the exact M-step installs its own table: the strings stay on the
+  // host, so heads of any length and a following exact M-step can read them
+  return c.install_host_table(t, su);
+}
+
 int hmc_resolve_all(hmc_ctx *h, double *ll, int *n_samples, uint64_t *r_e) {
   if (!h) return HMC_EARG;
   return h->c.estep(ll, n_samples, r_e);

@@ -542,7 +542,11 @@ int Ctx::bynum_replay(const MineArgs &, int ntot, int mnl, int mxl, int, uint64_
   if (int need = search(round)) { bynum_need = need; return MINE_RETRY; }
   max_num = std::max(max_num, (int)out.size());
   while ((int)out.size() < max_num && theta > 1e-38) {
-    if (stack.empty()) break;  // nothing left to accept: later rounds change nothing
+    if (stack.empty()) {  // nothing left to accept: the remaining searches only lower the threshold
+      last_size = (int)out.size();
+      while (theta > 1e-38) theta *= 0.9;
+      break;
+    }
     last_size = (int)out.size();
     theta *= 0.9;
     ++round;

@@ -431,6 +431,21 @@ class HaploModel:
                                            _p(freq, C.c_double), _p(tp, C.c_double), _p(succ, C.c_int32),
                                            _p(last, C.c_int32)))
 
+    def set_patterns_spelled(self, pt: dict):
+        """set_patterns from a table as `patterns()` returns it, strings and
+        prefix frequencies included: head_len > 1 and a following exact M-step
+        work on it."""
+        self._push_params()
+        al = np.ascontiguousarray(pt["alleles"], np.int32)
+        a = lambda x, t: np.ascontiguousarray(x, t)
+        start, length, succ = a(pt["start"], np.int32), a(pt["len"], np.int32), a(pt["succ"], np.int32)
+        freq, prefix, tp = a(pt["freq"], np.float64), a(pt["prefix"], np.float64), a(pt["tp"], np.float64)
+        if succ.shape != (len(start), self.amax):
+            raise ValueError(f"succ must be [{len(start)}][{self.amax}]")
+        self._check(lib().hmc_set_patterns_spelled(self._h, len(start), _p(start, C.c_int32), _p(length, C.c_int32),
+                                                   _p(al, C.c_int32), al.shape[1], _p(freq, C.c_double),
+                                                   _p(prefix, C.c_double), _p(tp, C.c_double), _p(succ, C.c_int32)))
+
     # ---------------------------------------------------------------- E-step
     def resolve_all(self) -> tuple[float, int, int]:
         """HaploModel::resolveAll; returns (log-likelihood, samples, R_E)."""

@@ -211,6 +211,13 @@ int hmc_get_patterns(hmc_ctx *ctx, int32_t *start, int32_t *len, double *freq, d
  * the pattern's last allele; succ as above. */
 int hmc_set_patterns(hmc_ctx *ctx, int P, const int32_t *start, const int32_t *len, const double *freq,
                      const double *tp, const int32_t *succ, const int32_t *last_symbol);
+/* The same with every pattern's whole string, alleles[P][maxlen] as
+ * hmc_get_patterns returns them, and its prefix frequency.  The strings are
+ * kept, so unlike hmc_set_patterns the table may have head_len > 1 and may be
+ * followed by an exact M-step. */
+int hmc_set_patterns_spelled(hmc_ctx *ctx, int P, const int32_t *start, const int32_t *len, const int32_t *alleles,
+                             int maxlen, const double *freq, const double *prefix, const double *tp,
+                             const int32_t *succ);
 
 /* ---- E-step: HaploModel::resolveAll (HaploModel.cpp:79-115) ------------
  * Resolves every individual of this rank's shard with HaploBuilder::resolve

@@ -224,18 +224,49 @@ def estep(alleles: np.ndarray, pt: dict, head_len: int):
 
 
 # ----------------------------------------------------------------- mining ----
+def matcher(alleles: np.ndarray, samples=None):
+    """The matching state of a mining candidate and its extension by one
+    symbol, shared by `mine` and set_enumeration.find_patterns_by_num.
+
+    Frequencies: from the genotypes (getMatchingFrequency, PatternManager.cpp:
+    267-291) the sum over individuals that match at every locus (an allele
+    missing or equal) of the product over loci of half the sum, over the two
+    alleles, of 1 if equal or the allele's frequency if missing, divided by N;
+    from `samples` = (haplotypes[H][L], weights[H]) the matching weights over
+    all weights (checkFrequencyWithExtension, :195-265).
+
+    Returns (root, extend): root = the state of the empty string, [(item,
+    factor)]; extend(state, k, a, af) = (state, frequency) of the string with
+    symbol a (allele frequency af) appended at locus k."""
+    N = alleles.shape[0]
+    if samples is None:
+        def extend(state, k, a, af):
+            nxt = []
+            for i, f in state:
+                b0, b1 = int(alleles[i, 0, k]), int(alleles[i, 1, k])
+                if b0 < 0 or b1 < 0 or b0 == a or b1 == a:
+                    x = (af if b0 < 0 else int(b0 == a)) + (af if b1 < 0 else int(b1 == a))
+                    nxt.append((i, f * x / 2))
+            return nxt, sum((f for _, f in nxt), Fraction(0)) / N
+
+        return [(i, Fraction(1)) for i in range(N)], extend
+    sal = np.asarray(samples[0])
+    sw = [Fraction(float(w)) for w in samples[1]]
+    tw = sum(sw)
+
+    def extend(state, k, a, af):
+        nxt = [(i, f) for i, f in state if sal[i, k] == a]
+        return nxt, sum((f for _, f in nxt), Fraction(0)) / tw
+
+    return [(i, sw[i]) for i in range(len(sw))], extend
+
+
 def mine(alleles: np.ndarray, min_freq: Fraction, min_len: int, max_len: int, samples=None):
     """PatternManager::searchPattern (PatternManager.cpp:100-144): per start
     locus a depth-first search from the empty string.  A string is extended by
     every allele of positive frequency if (freq >= min_freq or len < min_len),
     its end < L and len < max_len; it is stored if (freq >= min_freq or
-    len <= min_len) and len >= max(min_len, 1).
-
-    Frequencies: from the genotypes (getMatchingFrequency, :267-291) the sum
-    over individuals that match at every locus (an allele missing or equal)
-    of the product over loci of half the sum, over the two alleles, of 1 if
-    equal or the allele's frequency if missing, divided by N; from `samples`
-    = (haplotypes[H][L], weights[H]) the matching weights over all weights.
+    len <= min_len) and len >= max(min_len, 1).  Frequencies: `matcher`.
 
     Returns (stored, visited): stored[(start, symbols)] = (freq, prefix) with
     prefix the frequency without the last symbol (1 for length 1), visited =
@@ -244,29 +275,9 @@ def mine(alleles: np.ndarray, min_freq: Fraction, min_len: int, max_len: int, sa
     ta = allele_table(alleles)
     min_len = max(min_len, 1)
     max_len = max(L if max_len <= 0 else max_len, min_len)
-    if samples is not None:
-        sal = np.asarray(samples[0])
-        sw = [Fraction(float(w)) for w in samples[1]]
-        tw = sum(sw)
-
-    def extend(state, k, a, af):
-        nxt = []
-        if samples is None:
-            for i, f in state:
-                b0, b1 = int(alleles[i, 0, k]), int(alleles[i, 1, k])
-                if b0 < 0 or b1 < 0 or b0 == a or b1 == a:
-                    x = (af if b0 < 0 else int(b0 == a)) + (af if b1 < 0 else int(b1 == a))
-                    nxt.append((i, f * x / 2))
-            return nxt, sum((f for _, f in nxt), Fraction(0)) / N
-        for i, f in state:
-            if sal[i, k] == a:
-                nxt.append((i, f))
-        return nxt, sum((f for _, f in nxt), Fraction(0)) / tw
-
+    root, extend = matcher(alleles, samples)
     stored, visited = {}, []
     for s in range(L):
-        n0 = N if samples is None else len(sw)
-        root = [(i, Fraction(1) if samples is None else sw[i]) for i in range(n0)]
         stack = [((), root, Fraction(1), None)]
         while stack:
             al, state, freq, prefix = stack.pop()
@@ -305,13 +316,17 @@ def mstep(alleles: np.ndarray, prev: dict, head_len: int, keys):
     en = estep(alleles, prev, head_len)
     assert all(e is not None for e in en), "the exact M-step sums over every individual: no HEAD_QUIRK ones"
 
+    cache = memo(("expect", _digest(alleles), Table(prev).key, head_len), dict)  # shared by every call on this E-step
+
     def expect(s, al):
         if not al:
             return Fraction(N)
-        tot = Fraction(0)
-        for e in en:
-            tot += sum((p for h, p in e["marg"].items() if h[s:s + len(al)] == al), Fraction(0)) / e["total"]
-        return tot
+        if (s, al) not in cache:
+            tot = Fraction(0)
+            for e in en:
+                tot += sum((p for h, p in e["marg"].items() if h[s:s + len(al)] == al), Fraction(0)) / e["total"]
+            cache[s, al] = tot
+        return cache[s, al]
 
     return {(s, al): (expect(s, al), expect(s, al[:-1])) for s, al in keys}
 
